@@ -22,11 +22,19 @@ Multi-GPU: one process per GPU.  `python bench.py --gpus N` starts its own N ran
 process, before this process touches a GPU); started under torch.distributed.run it is a rank.  Paths are sharded over
 ranks, no collective inside the hot path, one RCCL all_gather of the 64-byte result rows per step.
 
+A plain run (`bench.py --gpus G --steps N --warmup W`) does what the headline figure needs and nothing else: inputs, W warm-up
+steps, N timed steps, [--dump-outputs DIR: what the last timed step computed, as .npy files,] the JSON line.  Everything else this
+file measures or checks -- the nested-loop cross-check, the output stage and the resampler beside the hot path, the four BASELINE
+configurations as worded, the CPU baselines and the comparisons with the oracle -- runs with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
 import concurrent.futures as cf
+import ctypes
 import json
+import mmap
+import multiprocessing
 import os
 import subprocess
 import sys
@@ -179,6 +187,99 @@ def taught_points_f32(workload: str, seeds, n_target: int):
     return [(g[0], g[1]) for g in got], float(np.float32(got[0][2]))
 
 
+def _farm_job(job):
+    """worker of TaughtFarm: taught points of one seed into its slot of the shared buffer"""
+    k, seed = job
+    f = TaughtFarm.current
+    theta, cart, _ = WORKLOADS[f.workload]["gen"](seed, f.n_coarse)
+    for a, view in ((theta, f.theta), (cart, f.cart)):
+        if view is not None:
+            assert a.shape == view.shape[1:], (a.shape, view.shape)
+            view[k] = a
+    return k
+
+
+class TaughtFarm:
+    """taught_points_f32 on worker PROCESSES (the generator is Python and scipy: threads of one process spend most of their time
+    waiting for each other).  The workers are forked before this process touches a GPU and write the float32 points of every seed
+    into anonymous shared memory, in the order of the seeds; farm[k] / farm[a:b] wait for those paths only, so the first resampler
+    calls run while the later paths are still being generated.  Same values as taught_points_f32."""
+    current = None      # (what the forked workers see)
+
+    def __init__(self, workload, seeds, n_target):
+        w = WORKLOADS[workload]
+        self.workload, self.seeds = workload, list(seeds)
+        self.n_coarse = max(8, int(round(n_target / w["knots_per_coarse"])))
+        theta, cart, tres = w["gen"](self.seeds[0], self.n_coarse)     # shapes (every seed of a workload gives the same)
+        self.sres_in = float(np.float32(tres))
+        self._maps = []
+        self.theta, self.cart = self._shared(theta), self._shared(cart)
+        TaughtFarm.current = self
+        n_proc = max(1, min(len(self.seeds), os.cpu_count() or 1, 16))
+        self.pool = multiprocessing.get_context("fork").Pool(n_proc)
+        self._it = self.pool.imap(_farm_job, list(enumerate(self.seeds)), chunksize=8)
+        self._done = 0
+
+    def _shared(self, a):
+        if a is None:
+            return None
+        m = mmap.mmap(-1, len(self.seeds) * a.size * 4)
+        self._maps.append(m)
+        return np.frombuffer(m, np.float32).reshape((len(self.seeds),) + a.shape)
+
+    def __len__(self):
+        return len(self.seeds)
+
+    def _wait(self, n):
+        while self._done < n:
+            k = next(self._it)
+            assert k == self._done, (k, self._done)
+            self._done += 1
+        if self._done == len(self.seeds):
+            self.close()
+
+    def close(self):
+        """end the workers (after the last path has arrived, or when the run ends early)"""
+        if self.pool is not None:
+            if self._done < len(self.seeds):
+                self.pool.terminate()
+            else:
+                self.pool.close()
+            self.pool.join()
+            self.pool = None
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return [self[i] for i in range(*k.indices(len(self.seeds)))]
+        self._wait(k + 1)
+        return (self.theta[k] if self.theta is not None else None, self.cart[k] if self.cart is not None else None)
+
+
+class FlatResampled(capi.Resampled):
+    """capi.Resampled of taught points that already lie in ONE buffer, path after path as [nJ + nC][n] float64 rows (what
+    batotp_hip_resample takes): the constructor of the base class would copy them together once more"""
+
+    def __init__(self, ctx, prm, flat, n_in, sres_in):
+        C = ctypes
+        self.ctx, self.lib, self.L = ctx, ctx.library.lib, ctx.library
+        self.n_paths = len(n_in)
+        self.n_ch = prm.n_joints + prm.n_cart
+        assert not (prm.path_type == capi.PATH_BOTH and prm.n_cart == 6)
+        n_in = np.ascontiguousarray(n_in, dtype=np.int64)
+        assert flat.dtype == np.float64 and flat.flags.c_contiguous and flat.size == self.n_ch * int(n_in.sum())
+        sr = np.ascontiguousarray(sres_in, dtype=np.float64)
+        self.handle = C.c_void_p()
+        self.L.check(self.lib.batotp_hip_resample(ctx.handle, C.byref(prm), self.n_paths, n_in.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  flat.ctypes.data_as(C.POINTER(C.c_double)), sr.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  C.byref(self.handle)), "batotp_hip_resample")
+        self.n_knots = np.zeros(self.n_paths, dtype=np.int64)
+        self.sres = np.zeros(self.n_paths, dtype=np.float64)
+        self.status = np.zeros(self.n_paths, dtype=np.uint32)
+        self.L.check(self.lib.batotp_hip_resampled_info(self.handle, self.n_knots.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        self.sres.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        self.status.ctypes.data_as(C.POINTER(C.c_uint32))), "resampled_info")
+
+
 def widen(workload: str, taught):
     """[nJ + nC][n] float64 rows the device resampler takes (theta rows, then Cartesian rows; absent ones zero)"""
     cfg = WORKLOADS[workload]["cfg"]
@@ -202,7 +303,8 @@ class Inputs:
     # 8 MB per path).  Round 5 used 256: 129 calls for the headline's two passes, each with a 61 ms floor (one walk wavefront per path)
     CHUNK = 1024
 
-    def __init__(self, hip, workload, knots, seeds):
+    def __init__(self, hip, workload, knots, seeds, farm=None):
+        """farm: a TaughtFarm of the same workload, seeds and knots (started before the GPU was touched), or None"""
         self.hip, self.workload, self.K = hip, workload, len(seeds)
         self.seeds, self.knots_target = list(seeds), knots
         first = make_knots(workload, seeds[0], knots)        # the one-path route of the product: problem description, and the check below
@@ -225,7 +327,10 @@ class Inputs:
                 self.seeds = self.seeds + [self.seeds[-1] + 1 + k for k in range(max(32, self.K // 16))]
                 self.K = len(self.seeds)
             self.n_knots, self.sres = np.zeros(self.K, np.int64), np.zeros(self.K)
-            self.taught, self.sres_in = taught_points_f32(workload, self.seeds, knots)
+            if farm is not None and farm.seeds == self.seeds:
+                self.taught, self.sres_in = farm, farm.sres_in       # (paths arrive while the first chunks are resampled)
+            else:
+                self.taught, self.sres_in = taught_points_f32(workload, self.seeds, knots)
             self.one_path_check = None
             feasible = np.ones(self.K, bool)
             for k0, rs in self._chunks():
@@ -251,6 +356,7 @@ class Inputs:
                     tb.close()
                 rs.close()
             hip.trim()
+            self.taught = self.taught[0:self.K]       # (a plain list from here on)
             if self.K > want:
                 ok = [p for p in range(self.K) if feasible[p]]
                 self.skipped = self.K - len(ok)
@@ -263,7 +369,8 @@ class Inputs:
                 self.n_knots, self.sres, self.K = self.n_knots[ok], self.sres[ok], want
             self._data = f"synthetic: {self.K} distinct seeded spline paths per GPU (taught points -> knots by the device resampler)"
         else:
-            with cf.ThreadPoolExecutor(max_workers=min(self.K, os.cpu_count() or 1)) as ex:
+            # (every make_knots is a process with a HIP context of its own: at most 12 at a time)
+            with cf.ThreadPoolExecutor(max_workers=min(self.K, os.cpu_count() or 1, 12)) as ex:
                 rest = list(ex.map(lambda s: make_knots(workload, s, knots), seeds[1:]))
             self.base = [first] + rest
             self.n_knots = np.array([b[0].shape[1] for b in self.base], np.int64)
@@ -291,10 +398,43 @@ class Inputs:
             done += 1
         return done
 
+    def _widen_chunk(self, k0, pool):
+        """widen() of the paths [k0, k0 + CHUNK) straight into one buffer, path after path (the buffers of chunk i and i + 2 are the
+        same memory); returns (buffer, points per path)"""
+        taught = self.taught[k0:k0 + self.CHUNK]
+        nJ = self.prm.n_joints
+        n_in = np.array([(t[0] if t[0] is not None else t[1]).shape[1] for t in taught], np.int64)
+        off = np.concatenate([[0], np.cumsum(n_in)]) * self.nC_in
+        slot = (k0 // self.CHUNK) % 2
+        if self._bufs[slot] is None or self._bufs[slot].size < int(off[-1]):
+            self._bufs[slot] = np.empty(int(off[-1]))
+        flat = self._bufs[slot][: int(off[-1])]
+
+        def one(i):
+            x = flat[off[i]:off[i + 1]].reshape(self.nC_in, int(n_in[i]))
+            theta, cart = taught[i]
+            if theta is not None:
+                x[:nJ] = theta.astype(np.float32, copy=False)
+            else:
+                x[:nJ] = 0.0
+            if cart is not None:
+                x[nJ:] = cart.astype(np.float32, copy=False)
+            else:
+                x[nJ:] = 0.0
+        list(pool.map(one, range(len(taught))))
+        return flat, n_in
+
     def _chunks(self):
-        for k0 in range(0, self.K, self.CHUNK):
-            xs = [widen(self.workload, t) for t in self.taught[k0:k0 + self.CHUNK]]
-            yield k0, capi.Resampled(self.hip, self.prm, xs, [self.sres_in] * len(xs))
+        # the host side of chunk i + 1 (widening the float32 points) runs while the device resamples chunk i
+        self._bufs = [None, None]
+        with cf.ThreadPoolExecutor(max_workers=8) as pool, cf.ThreadPoolExecutor(max_workers=1) as ahead:
+            nxt = ahead.submit(self._widen_chunk, 0, pool)
+            for k0 in range(0, self.K, self.CHUNK):
+                flat, n_in = nxt.result()
+                if k0 + self.CHUNK < self.K:
+                    nxt = ahead.submit(self._widen_chunk, k0 + self.CHUNK, pool)
+                yield k0, FlatResampled(self.hip, self.prm, flat, n_in, [self.sres_in] * len(n_in))
+        self._bufs = [None, None]
 
     def oracle_knots(self, k):
         """CHECKER (cpu_baseline leg and tests only): (y, sres) of distinct path k from the ORACLE's resampler -- independent
@@ -401,9 +541,22 @@ def plan_chunks(B, K, limit):
     return [min(bc, B - i * bc) for i in range((B + bc - 1) // bc)] if B else []
 
 
+def bench_seeds(cfg_name, rank, world, paths_override=0, distinct_override=0):
+    """seeds of the distinct paths of this rank's share of a configuration"""
+    c = CONFIGS[cfg_name]
+    total_paths = paths_override or c["paths"]
+    lo, B = 0, total_paths
+    if c["scaling"] == "strong":
+        lo, hi = bdist.shard_range(total_paths, rank, world)
+        B = hi - lo
+    K = max(1, min(distinct_override or c["distinct"], max(B, 1)))
+    return [1000 + (rank * 100003 + lo) + k for k in range(K)]
+
+
 def measure(hip, cfg_name, rank, world, steps, warmup, dist_ctx, paths_override=0, knots_override=0, group=0, ppw=0,
-            coefficient_rows=False, distinct_override=0, keep=False, lean=False):
-    """run one configuration on this rank's share; returns (result dict, kept objects or None)"""
+            coefficient_rows=False, distinct_override=0, keep=False, lean=False, digests=True, farm=None):
+    """run one configuration on this rank's share; returns (result dict, kept objects or None).  digests: keep the digests of the
+    first knots as well (what the CPU baseline compares with the oracle's resampler; a resampler call of its own)"""
     import torch
     c = CONFIGS[cfg_name]
     workload = c["workload"]
@@ -414,8 +567,8 @@ def measure(hip, cfg_name, rank, world, steps, warmup, dist_ctx, paths_override=
         B = hi - lo
     else:
         lo, B = 0, total_paths
-    K = max(1, min(distinct_override or c["distinct"], max(B, 1)))
-    seeds = [1000 + (rank * 100003 + lo) + k for k in range(K)]
+    seeds = bench_seeds(cfg_name, rank, world, paths_override, distinct_override)
+    K = len(seeds)
     hip.set_sweep_group(group)
     hip.set_paths_per_wave(ppw)
     # a TILED batch (fewer distinct paths than paths: profiling passes, --distinct) of a velocity / acceleration-only problem is
@@ -425,7 +578,7 @@ def measure(hip, cfg_name, rank, world, steps, warmup, dist_ctx, paths_override=
     wcfg0 = WORKLOADS[workload]["cfg"]
     multi_path_wavefronts = not (wcfg0.get("trq_on") or wcfg0.get("cart_vel_on") or wcfg0.get("cart_acc_on"))
     hip.set_path_order(0 if (B > K and multi_path_wavefronts) else 1)
-    inp = Inputs(hip, workload, knots, seeds)
+    inp = Inputs(hip, workload, knots, seeds, farm)
     prob = capi.Problem.from_buffer_copy(bytes(inp.prob))
     if (prob.flags & capi.F_NO_SAMPLES) and not coefficient_rows:
         prob.flags |= capi.F_COMPACT_SPLINES  # same results, half the spline bytes per knot: room for more paths per GPU
@@ -657,7 +810,7 @@ def measure(hip, cfg_name, rank, world, steps, warmup, dist_ctx, paths_override=
     kept = None
     if keep:
         kept = dict(batch=batch, inp=inp, prob=prob, cap=cap, res=res, K=K, B=B, chunk0=chunk_sizes[0] if B else 0,
-                    knot_digests=inp.device_knot_digests(64) if (rank == 0 and B) else [])
+                    knot_digests=inp.device_knot_digests(64) if (digests and rank == 0 and B) else [])
     elif batch is not None:
         batch.close()
     return out, kept
@@ -787,6 +940,53 @@ def cpu_baseline(kept, budget_s, out_prm=None, want_output=False, max_distinct=1
     return info, err, mism, th0
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files of all ranks together
+DUMP_CURVE_BYTES = 48 << 20     # ... of which the curves of the seeded sample of paths may take this much
+
+
+def dump_outputs(dirname, rank, world, kept):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float64 .npy files -- the result row
+    of every path of this rank (one array per field of struct batotp_path_result) and the integrated curves (s, sdot) of a fixed,
+    seeded sample of the paths of the resident batch: the forward curve, and the reverse curve where the batch still has it
+    (BATOTP_F_CURVES_IN_PLACE: the forward sweep has overwritten it).  Same arguments, same inputs, same sample: two builds can
+    be compared file by file.  Ranks other than 0 write <name>.rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    written = [0]
+
+    def save(name, a):
+        f = os.path.join(dirname, f"{name}{sfx}.npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float64))
+        written[0] += os.path.getsize(f)
+    res, batch = kept["res"], kept["batch"]
+    for f in capi.RESULT_DTYPE.names:
+        save("result_" + f, res[f])
+    n_res = kept["chunk0"]
+    if batch is None or not n_res:
+        return
+    rows = batch.results()[:n_res]
+    which = [("fwd", +1, "n_fwd")] + ([] if (kept["prob"].flags & capi.F_CURVES_IN_PLACE) else [("rev", -1, "n_rev")])
+    order = np.random.default_rng(20240607).permutation(n_res)
+    budget = DUMP_CURVE_BYTES // max(world, 1)
+    picked, used = [], 0
+    for p in order:
+        need = 16 * sum(int(max(rows[field][p], 0)) for _, _, field in which)      # (s, sdot) of every curve written for the path
+        if used + need > budget:
+            break
+        picked.append(int(p))
+        used += need
+        if len(picked) == 64:
+            break
+    picked.sort()
+    save("curve_paths", picked)
+    for tag, w, field in which:
+        cs = [batch.curve(p, w) for p in picked]
+        save(f"curve_{tag}_offsets", np.concatenate([[0], np.cumsum([c[0].shape[0] for c in cs])]))
+        save(f"curve_{tag}_s", np.concatenate([c[0] for c in cs]) if cs else np.zeros(0))
+        save(f"curve_{tag}_sdot", np.concatenate([c[1] for c in cs]) if cs else np.zeros(0))
+    assert written[0] * max(world, 1) <= DUMP_LIMIT_BYTES, (written[0], world)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks as a CHILD process (this process never
@@ -885,7 +1085,15 @@ def main():
     ap.add_argument("--coefficient-rows", action="store_true",
                     help="keep four coefficients per knot and channel instead of the compact (value, second derivative) form")
     ap.add_argument("--launch-check", action="store_true", help="exercise launcher, sharding and gather only (gloo, no GPU work)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: nested-loop cross-check, output stage, resampler, the BASELINE configurations as worded, CPU "
+                         "baselines and the comparisons with the oracle (the --no-* switches take parts of it out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64): the result rows and the curves of a "
+                         "seeded sample of paths")
     args = ap.parse_args()
+    if not args.full:     # a plain run: the timed steps and nothing beside them
+        args.no_sides = args.no_as_worded = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))   # nothing above touched a GPU
@@ -897,6 +1105,13 @@ def main():
                          f"through torch.distributed.run --nproc-per-node {args.gpus}")
     if args.launch_check:
         return launch_check(args, rank, world)
+
+    # the taught points of the headline's paths come from worker processes, forked here: nothing has touched a GPU yet
+    farm = None
+    wl = CONFIGS[args.config]["workload"]
+    farm_seeds = bench_seeds(args.config, rank, world, args.paths, args.distinct)
+    if device_resamplable(wl) and not WORKLOADS[wl]["cfg"]["is_parallel"] and len(farm_seeds) > 64:
+        farm = TaughtFarm(wl, farm_seeds, args.knots or CONFIGS[args.config]["knots"])
 
     import torch
     import torch.distributed as dist
@@ -924,8 +1139,15 @@ def main():
 
     default_run = args.config == "fill7" and not args.paths and not args.knots
     cpu_job = (None, None)
-    out, kept = measure(hip, args.config, rank, world, args.steps, args.warmup, dist_ctx, args.paths, args.knots, args.group, args.ppw,
-                        args.coefficient_rows, args.distinct, keep=True, lean=args.lean)
+    try:
+        out, kept = measure(hip, args.config, rank, world, args.steps, args.warmup, dist_ctx, args.paths, args.knots, args.group, args.ppw,
+                            args.coefficient_rows, args.distinct, keep=True, lean=args.lean, digests=not (args.no_sides or args.no_cpu_baseline),
+                            farm=farm)
+    finally:
+        if farm is not None:
+            farm.close()      # (no worker outlives a run that ends early)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, kept)
     workload = CONFIGS[args.config]["workload"]
     prob, batch = kept["prob"], kept["batch"]
     vel_acc_only = not (prob.flags & (capi.F_TRQ_ON | capi.F_CART_VEL_ON | capi.F_CART_ACC_ON))

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """fp64 golden vectors read out of THE REFERENCE BINARY while it runs -- build container only (needs /root/reference and
-/opt/rocm/bin/rocgdb).
+the gdb build that ships with the ROCm toolchain; another gdb with Python scripting can be named in the environment variable GDB).
 
 oracle/make_golden.py pins the oracle with the files the reference writes, which are float32 (ba.cpp:2745-2748 casts on write).
-This script closes that gap (SURVEY.md 8c iii-v): it runs the reference's prebuilt, unstripped bin/batest under rocgdb in batch
+This script closes that gap (SURVEY.md 8c iii-v): it runs the reference's prebuilt, unstripped bin/batest under the ROCm toolchain's gdb in batch
 mode on the same case directories and reads the reference's OWN fp64 memory:
 
   * at the return of each BATOTP::BA::sweep (ba.cpp:979-1195): traj.sMVC, traj.sdot (every point, raw doubles), traj.nPts,
@@ -36,7 +36,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import make_golden as mg  # noqa: E402  (the case builders)
 
-GDB = "/opt/rocm/bin/rocgdb"
+
+
+def find_gdb():
+    """the debugger the fixtures were read with: the gdb build in the ROCm toolchain's bin directory (it debugs the reference's HOST
+    binary here, nothing on a GPU); $GDB overrides, a plain gdb on the PATH is the last resort"""
+    import glob
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    found = [os.environ.get("GDB")] + sorted(glob.glob(os.path.join(rocm, "bin", "*gdb"))) + [shutil.which("gdb")]
+    for g in found:
+        if g and os.access(g, os.X_OK):
+            return g
+    raise SystemExit("make_golden_f64.py: no gdb found (set GDB)")
+
+
+GDB = find_gdb()
 OFFSETS_TOOL = os.path.join(ROOT, "oracle", "_build", "traj_offsets")
 SAMPLES_PER_SWEEP = 128
 
@@ -176,7 +190,7 @@ def run_case(name):
            "n_rev_pts": int(curves["rev"][0].size), "n_fwd_pts": int(curves["fwd"][0].size),
            "sha256_rev_f64": hashlib.sha256(curves["rev"][0].tobytes() + curves["rev"][1].tobytes()).hexdigest(),
            "sha256_fwd_f64": hashlib.sha256(curves["fwd"][0].tobytes() + curves["fwd"][1].tobytes()).hexdigest(),
-           "reference": "fp64 memory of the prebuilt /root/reference/bin/batest read under rocgdb at the return of BA::sweep"}
+           "reference": "fp64 memory of the reference's prebuilt bin/batest read under the ROCm toolchain's gdb (batch mode) at the return of BA::sweep"}
     json.dump(out, open(os.path.join(dst, "expected_f64.json"), "w"), indent=1)
     if full:
         np.savez_compressed(os.path.join(dst, "ref_curves_f64.npz"), rev_s=curves["rev"][0], rev_sd=curves["rev"][1],

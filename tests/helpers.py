@@ -290,7 +290,7 @@ def f64_digest(s, sd):
 
 def assert_matches_reference_f64(case, out):
     """fp64 bit equality with what the reference binary held in memory at the return of each BA::sweep (traj.sMVC, traj.sdot,
-    traj.tTotalTraj read under rocgdb by oracle/make_golden_f64.py): every point of both curves for the small cases, their
+    traj.tTotalTraj read under the ROCm toolchain's gdb by oracle/make_golden_f64.py): every point of both curves for the small cases, their
     sha256 for the BASELINE-size ones"""
     f = os.path.join(case.dir, "expected_f64.json")
     if not os.path.exists(f):

@@ -4,7 +4,7 @@
     python tools/bench_output.py --workload gen7 --paths 512 --knots 100000
 
 Prints one JSON line (best of the calls after the first, which allocates the context's workspace).  Parity is the tests'
-business (tests/test_gpu_output.py); bench.py compares the rows with the oracle's on every default run."""
+business (tests/test_gpu_output.py); bench.py --full compares the rows with the oracle's."""
 import argparse
 import json
 import os

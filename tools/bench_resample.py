@@ -5,7 +5,7 @@
 
 Prints one JSON line: knots per second and milliseconds (cold = first call of the process, which allocates the
 context's workspaces; warm = best of the following calls).  Parity is the tests' business (tests/test_gpu_resample.py);
-bench.py compares the knots with the host resampler's on every run."""
+bench.py --full compares the knots with the host resampler's."""
 import argparse
 import json
 import os

@@ -65,7 +65,7 @@ def main():
     ap.add_argument("--knots", type=int, default=50000)
     ap.add_argument("--seeds", type=int, default=1024)
     ap.add_argument("--seed0", type=int, default=7000)
-    ap.add_argument("--jobs", type=int, default=64)
+    ap.add_argument("--jobs", type=int, default=12)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--resident", type=int, default=1024, help="paths of a resident batch sweeping meanwhile (0: none)")
     ap.add_argument("--idle", action="store_true", help="the resident batch sweeps once and then sits idle (what the red test had)")

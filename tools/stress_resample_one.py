@@ -89,7 +89,7 @@ def worker(k, wave, knots, life, per_ctx, out, q, alternate=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--jobs", type=int, default=64)
+    ap.add_argument("--jobs", type=int, default=12)
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--life", type=float, default=60.0)
     ap.add_argument("--calls-per-context", type=int, default=8)

@@ -50,7 +50,7 @@ def worker(k, n, seconds, q):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--jobs", type=int, default=64)
+    ap.add_argument("--jobs", type=int, default=12)
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--n", type=int, default=34000)
     ap.add_argument("--resident", type=int, default=1024, help="paths of a resident batch sweeping meanwhile (0: none)")
