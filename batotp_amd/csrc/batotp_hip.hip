@@ -11,6 +11,7 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "batotp_hip.h"
@@ -46,9 +47,7 @@ using namespace bk;
 
 // k_sweep8, reverse sweep: the certificate block runs once this many eighths of a wavefront's live paths wait for it (measured on the
 // headline batch, profiles/r06_a_*; batotp_hip_set_cert_hold overrides)
-#ifndef BATOTP_CERT_HOLD_DEFAULT
-#define BATOTP_CERT_HOLD_DEFAULT 3
-#endif
+constexpr int BATOTP_CERT_HOLD_DEFAULT = 3;
 
 // ---------------------------------------------------------------------------------------------
 // error bookkeeping
@@ -134,6 +133,19 @@ struct batotp_ctx
    char builtWith[192] = "";    // toolchain the gate compares (the real one; only a -DBATOTP_TEST_HOOKS build lets a test override it)
 };
 
+// What a sweep launches (planSweep decides it, launchSweep / launchSweep1 launch it, the batch keeps the last one per direction)
+struct SweepPlan
+{
+   int feat = 0;      // featureLevel
+   bool uni = false;  // every path has uniform knot sites
+   int lanes = 0;     // lanes per path: 64 = k_sweep1 (sweep1.hip.h), otherwise G of k_sweep / k_sweep8; 0 = no sweep (yet, or not possible)
+   int ppw = 0;       // paths per wavefront
+   int hold = -1, touch = 0, ff = 0, holdc = 0; // as in SweepArgs
+   bool flat = false;   // k_sweep / k_sweep8: the flat stage / bisection loop
+   bool form8 = false;  // ... as k_sweep8 (sweep8.hip.h)
+   int ff1 = 0;         // k_sweep1, torque limits: form of the certified fast-forward (template parameter FF)
+};
+
 struct batotp_batch
 {
    batotp_ctx *ctx = nullptr;
@@ -145,7 +157,6 @@ struct batotp_batch
    std::vector<PathInfo> pinfo; // host mirror
    bool needPar = false;        // some path may run the parallel-mechanism torque branch
    bool k3Pending = false;      // an overlapped per-knot evaluation may still be running on ctx->stream2
-   bool lastForm8[2] = {false, false}; // the most recent sweep per direction ran k_sweep8
    bool compact = false;        // BATOTP_F_COMPACT_SPLINES: (value, second derivative) pairs in dKM, there is no dCoef
    bool pairsAll = false;       // ... of a problem with Cartesian / dynamics channels: ALL C channels are pairs (kmC = C), the kernels of the
                                 // coefficient-row layouts (FEAT >= 0) form their rows from them, no sample and no dynamics array exists
@@ -184,7 +195,7 @@ struct batotp_batch
 
    hipEvent_t ev[5][2] = {};
    bool evValid[5] = {};
-   int lastLanes[2] = {0, 0}, lastPpw[2] = {0, 0}, lastHold[2] = {-1, -1}; // reverse, forward: what the last launch used
+   SweepPlan lastPlan[2]; // reverse, forward: what the last launch used
 };
 
 // debug aid (batotp_hip_set_poison): memory a stage is about to use is filled with 0xFF bytes -- NaNs as doubles, -1 as integers -- so
@@ -1209,6 +1220,22 @@ static int featureLevel(const batotp_batch *b)
    return (b->compact && !b->pairsAll) ? -1 : 0;
 }
 
+// ... and the call of fn(Int<F>()) for that level F: a generic lambda launches the kernel instantiation of the level
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class Fn>
+static void withFeature(int feat, Fn &&fn)
+{
+   switch (feat)
+   {
+   case -1: fn(Int<-1>()); break;
+   case 0: fn(Int<0>()); break;
+   case 1: fn(Int<1>()); break;
+   case 2: fn(Int<2>()); break;
+   default: fn(Int<3>()); break;
+   }
+}
+
 static int readyForSweep(const batotp_batch *b)
 {
    if (!b->sitesSet) return BATOTP_ERR_STATE;
@@ -1236,7 +1263,8 @@ extern "C" int batotp_hip_pointwise_mvc(batotp_batch *b)
    // cable robot (C = 18) 125 vs 53 ms.  BATOTP_K3_TILE=1 switches it on for experiments.
    const bool useTile = false;
    // velocity / acceleration-only problems: the kernel written for them (same bits; batotp_hip_set_k3_form(ctx, 0) runs the general one)
-   const bool formVA = !grouped && b->ctx->k3Form == 1 && featureLevel(b) <= 0;
+   const int feat = featureLevel(b);
+   const bool formVA = !grouped && b->ctx->k3Form == 1 && feat <= 0;
    const size_t ldsBytes = useTile ? sizeof(double) * (size_t)bs * (size_t)(b->P.C * 4 + 2) : 0;
    // overlap: K3 reads what the precompute wrote and nothing reads K3's output before the caller downloads it, so it
    // can share the GPU with the sweeps (second stream, joined by get_results / synchronize / the next precompute)
@@ -1251,32 +1279,23 @@ extern "C" int batotp_hip_pointwise_mvc(batotp_batch *b)
       HIP_TRY(hipStreamWaitEvent(k3s, b->ctx->evJoin, 0));
    }
    hipEventRecord(b->ev[2][0], k3s);
-#define LAUNCH_K3(F)                                                                                                                     \
-   do {                                                                                                                                  \
-      if (grouped)                                                                                                                       \
-         for (int64_t first = 0; first < b->totalKnots; first += sliceKnots)                                                            \
-         {                                                                                                                               \
-            const int64_t cnt = (b->totalKnots - first) < sliceKnots ? (b->totalKnots - first) : sliceKnots;                            \
-            hipLaunchKernelGGL(k_pointwise_grp<F>, dim3((unsigned)((cnt + knotsPerBlock - 1) / knotsPerBlock)), dim3(bs), 0,           \
-                               k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, first,         \
-                               first + cnt, mvcSlot);                                                                                             \
-         }                                                                                                                               \
-      else if (formVA && F <= 0)                                                                                                        \
-         hipLaunchKernelGGL(k_pointwise_va<(F <= 0 ? F : 0)>, dim3((unsigned)((b->totalKnots + K3V_BLOCK - 1) / K3V_BLOCK)), dim3(K3V_BLOCK), 0, k3s, b->P,  \
-                            b->dPinfo, b->B, b->dP, b->dSC, b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots, mvcSlot,           \
-                            b->ctx->fastForward);                                                                                         \
-      else hipLaunchKernelGGL(k_pointwise<F>, dim3(grid), dim3(bs), ldsBytes, k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC,      \
-                              b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots, useTile ? 1 : 0, mvcSlot);                                      \
-   } while (0)
-   switch (featureLevel(b))
-   {
-   case -1: LAUNCH_K3(-1); break;
-   case 0: LAUNCH_K3(0); break;
-   case 1: LAUNCH_K3(1); break;
-   case 2: LAUNCH_K3(2); break;
-   default: LAUNCH_K3(3); break;
-   }
-#undef LAUNCH_K3
+   withFeature(feat, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      if (grouped)
+         for (int64_t first = 0; first < b->totalKnots; first += sliceKnots)
+         {
+            const int64_t cnt = (b->totalKnots - first) < sliceKnots ? (b->totalKnots - first) : sliceKnots;
+            hipLaunchKernelGGL(k_pointwise_grp<F>, dim3((unsigned)((cnt + knotsPerBlock - 1) / knotsPerBlock)), dim3(bs), 0, k3s, b->P, b->dPinfo,
+                               b->B, b->dP, b->dSC, b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, first, first + cnt, mvcSlot);
+         }
+      else if (formVA && F <= 0)
+         hipLaunchKernelGGL(k_pointwise_va<(F <= 0 ? F : 0)>, dim3((unsigned)((b->totalKnots + K3V_BLOCK - 1) / K3V_BLOCK)), dim3(K3V_BLOCK), 0,
+                            k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots,
+                            mvcSlot, b->ctx->fastForward);
+      else
+         hipLaunchKernelGGL(k_pointwise<F>, dim3(grid), dim3(bs), ldsBytes, k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef,
+                            b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots, useTile ? 1 : 0, mvcSlot);
+   });
    hipEventRecord(b->ev[2][1], k3s);
    b->evValid[2] = true;
    HIP_TRY(hipGetLastError());
@@ -1456,19 +1475,87 @@ extern "C" int batotp_hip_flat_loop_status(batotp_ctx *ctx, int32_t *status)
 extern "C" int batotp_hip_last_sweep_launch(batotp_batch *b, int32_t dir, int32_t *lanes, int32_t *paths_per_wave, int32_t *hold)
 {
    if (!b || (dir != 1 && dir != -1)) return BATOTP_ERR_ARG;
-   const int k = dir == -1 ? 0 : 1;
-   if (b->lastLanes[k] == 0) return BATOTP_ERR_STATE;
-   if (lanes) *lanes = b->lastLanes[k];
-   if (paths_per_wave) *paths_per_wave = b->lastPpw[k];
-   if (hold) *hold = b->lastHold[k];
+   const SweepPlan &p = b->lastPlan[dir == -1 ? 0 : 1];
+   if (p.lanes == 0) return BATOTP_ERR_STATE;
+   if (lanes) *lanes = p.lanes;
+   if (paths_per_wave) *paths_per_wave = p.ppw;
+   if (hold) *hold = p.flat ? p.hold : -1;
    return BATOTP_OK;
 }
 
-template <int G>
-static void launchSweep(batotp_batch *b, SweepArgs &a)
+// Which kernel a sweep runs and in which shape.  Everything is decided here; the launch functions below launch what the plan says.
+// lanes == 0 in the result: the batch cannot be swept (pairs for all channels where k_sweep1 does not apply).
+// Consults the gate of the flat loop (whose canary launches sweeps of its own): call it before the sweep's timed region starts.
+static SweepPlan planSweep(const batotp_batch *b, int dir)
 {
-   const int maxPpw = 64 / G;
-   int ppw = b->ctx->pathsPerWave;
+   const batotp_ctx *ctx = b->ctx;
+   const int k = dir == -1 ? 0 : 1;
+   SweepPlan p;
+   p.feat = featureLevel(b);
+   p.uni = true;
+   for (int i = 0; i < b->B; ++i) p.uni = p.uni && b->pinfo[i].uniform;
+   // the one-path-per-wavefront kernel of sweep1.hip.h applies to every constraint family except the torque limits of a parallel
+   // mechanism that is still parallel (the cable robot without isPar2Ser: an LU solve per joint and limit); uniform knot sites
+   const bool sweep1Applies = p.feat <= 2 && p.uni;
+
+   int lanes = ctx->sweepGroup;
+   if (lanes == 0)
+   {
+      // automatic: while the batch cannot fill the 8-lane layout anyway (<= 4 paths per SIMD), give a
+      // path 16 lanes and split the interval bounds over the two halves (fewer instructions per check)
+      // automatic (measured on UR6, N = 100k): up to ~2k paths the batch is latency-bound and the
+      // 32-lane layout (four bisection candidates per pass) wins; beyond that the 8-lane layout, which
+      // packs more paths per wavefront, has the higher throughput
+      lanes = (b->B <= (dir == -1 ? 2048 : 1024)) ? 32 : 8;
+      // ... and where every path has a wavefront to itself anyway, the kernel written for that case (sweep1.hip.h).  It also
+      // wins for a while beyond that, with its wavefronts queueing for the two slots per SIMD its registers leave: the 8-lane
+      // layout at 2-4 paths per wavefront is latency-bound and slower (GEN7DOF, N = 5e4, reverse: 3072 paths 944 vs 1882 ms,
+      // 6144 paths 1784 vs 2024, 8192 paths 2328 vs 2137; forward: 3072 paths 923 vs 981, 4096 paths 1118 vs 1031; UR6 alike)
+      // (round 4, against k_sweep8 instead of k_sweep -- N = 5e4, reverse / forward ms: 2048 paths 594 / 516 vs 1117 / 687, 4096 paths
+      //  1051 / 1008 vs 1231 / 738: the reverse crossover moved from ~6000 to ~4900 paths, the forward one stays near 3000)
+      if (sweep1Applies && b->B <= (dir == -1 ? 4608 : 3072)) lanes = 64;
+      // (round 5, compact velocity / acceleration-only batches: with TWO paths per wavefront the one-path kernel keeps its lead over
+      //  the 8-lane layout up to ~7600 paths in the reverse and ~5000 in the forward sweep -- GEN7DOF, N = 5e4, reverse / forward ms,
+      //  one path | two paths | 8 lanes: 4096 paths 1055 / 1004 | 902 / 646 | 1345 / 738; 6144 paths 1460 / 1480 | 1152 / 1050 |
+      //  1460 / 868; 8192 paths 1905 / 1950 | 1588 / 1260 | 1505 / 868: profiles/r05_i_*; one or two is picked below)
+      if (sweep1Applies && p.feat == -1 && b->B <= (dir == -1 ? 7600 : 5000)) lanes = 64;
+   }
+   if (b->pairsAll)
+   {
+      // rows exist in the LDS windows of the one-path-per-wavefront kernel only
+      if (!sweep1Applies) return p;
+      lanes = 64;
+   }
+   if (lanes == 64 && !sweep1Applies) lanes = 32; // a parallel mechanism's torque limits, uploaded sites: the general kernel
+   p.lanes = lanes;
+
+   if (lanes == 64)
+   {
+      p.hold = -1; p.touch = 0; p.ff = ctx->fastForward; p.holdc = 0;
+      const bool cableLines = p.feat == 2 && (b->P.flags & BATOTP_F_PARALLEL) != 0 && b->pairsAll;
+      // Two paths per wavefront (k_sweep1's NP = 2; the cable robot in serial form with every channel as pairs): where one path per
+      // wavefront would leave wavefronts queueing for the two slots per SIMD the kernel's registers allow, or where the caller asks
+      // for it (batotp_hip_set_paths_per_wave(ctx, 2) with 64 lanes per path).  Measured on BASELINE config 5 (N = 2e5, reverse +
+      // forward ms; profiles/r05_h_*): up to 2048 paths every path has a resident wavefront either way and the sweeps last as long as
+      // the slowest path -- 1147 + 1326 with one path per wavefront, 1238 + 1474 with two (a wavefront that serves two paths is 8-11 %
+      // slower); 3072 paths 1613 + 1496 against 1244 + 1479; 4096 paths 2159 + 2033 against 1228 + 1479.  The crossover is at ~2300.
+      const int want = ctx->pathsPerWave;
+      // ... and the compact velocity / acceleration-only layout (round 5; the batch sizes between the one-path kernel and k_sweep8)
+      const bool compactVA = p.feat == -1;
+      // (a two-path wavefront of this family is 20 % slower in the reverse sweep and as fast as a one-path wavefront in the forward
+      //  sweep: 2048 paths 713 / 513 against 596 / 515 ms; one-path wavefronts queue beyond 2048 paths: 3072 paths 775 / 829 ms
+      //  against 901 / 646)
+      const bool two = (cableLines && (want == 2 || (want <= 0 && b->B > 2304))) ||
+                       (compactVA && (want == 2 || (want <= 0 && b->B > (dir == -1 ? 3500 : 2304))));
+      p.ppw = two ? 2 : 1;
+      // the fast-forward of the bisection in the form that fits the mechanism: a parallel robot converted to serial form has
+      // a3 = 0 (tension bounds are lines in sdot^2), a serial chain has friction (bounds quadratic in sdot)
+      p.ff1 = (p.feat == 2 && (b->P.flags & BATOTP_F_PARALLEL) == 0) ? 1 : 0;
+      return p;
+   }
+
+   const int maxPpw = 64 / lanes;
+   int ppw = ctx->pathsPerWave;
    if (ppw <= 0)
    {
       // automatic: with few paths spread them over more wavefronts (latency-bound regime), with many
@@ -1477,28 +1564,23 @@ static void launchSweep(batotp_batch *b, SweepArgs &a)
       // iterations, whose count differs between the paths of a wavefront, so it prefers fewer
       // paths per wavefront than the forward sweep (measured, B = 4096: rev best at 2, fwd at 4).
       // rounded up: one path too many per wavefront costs little, a second round of wavefronts on the SIMDs costs a lot
-      ppw = (a.dir == -1) ? (b->B + 2047) / 2048 : (b->B + 1023) / 1024;
+      ppw = (dir == -1) ? (b->B + 2047) / 2048 : (b->B + 1023) / 1024;
       // forward, more than 4096 paths: two wavefronts per SIMD as well, but never fewer than the 4 paths per wavefront that
       // were best at 4096 (11 264 GEN7DOF paths: 2600 ms with 6 paths per wavefront / 1878 wavefronts, 2762 ms with 8 / 1408 --
       // 1.4 wavefronts per SIMD leaves the SIMDs with one wavefront idle while those with two finish)
-      if (a.dir == 1 && ppw > 4) ppw = std::max(4, (b->B + 2047) / 2048);
+      if (dir == 1 && ppw > 4) ppw = std::max(4, (b->B + 2047) / 2048);
    }
    if (ppw < 1) ppw = 1;
    if (ppw > maxPpw) ppw = maxPpw;
-   a.ppw = ppw;
+   p.ppw = ppw;
    // software prefetch of the lines ahead of the cursors: the reverse sweep always (descending addresses: -17 % at 4096 paths);
    // the forward sweep only while every path has a wavefront to itself -- there the sweep waits a third of its time for the
    // dependent loads of segment changes (SQ_WAIT_ANY at B = 1, profiles/), with many paths per wavefront it cost +5 %
-   a.touch = (a.dir == -1) ? 1 : (ppw == 1 ? 3 : 0);
-   a.ff = sweep8FastForward(b->ctx);   // (the general kernel k_sweep reads no bit of it)
-   a.holdc = std::max(1, certHoldOf(b->ctx));
-   if (b->ctx->sweepTouch[a.dir == -1 ? 0 : 1] >= 0) a.touch = b->ctx->sweepTouch[a.dir == -1 ? 0 : 1];
-   const unsigned waves = (unsigned)((b->B + ppw - 1) / ppw);
-   const unsigned grid = (waves + (K4_BLOCK / 64) - 1) / (K4_BLOCK / 64);
-   bool uni = true;
-   for (int p = 0; p < b->B; ++p) uni = uni && b->pinfo[p].uniform;
-   hipStream_t st = b->ctx->stream;
-   int hold = b->ctx->sweepHold[a.dir == -1 ? 0 : 1];
+   p.touch = (dir == -1) ? 1 : (ppw == 1 ? 3 : 0);
+   p.ff = sweep8FastForward(ctx);   // (the general kernel k_sweep reads no bit of it)
+   p.holdc = std::max(1, certHoldOf(ctx));
+   if (ctx->sweepTouch[k] >= 0) p.touch = ctx->sweepTouch[k];
+   int hold = ctx->sweepHold[k];
    // automatic: the flat stage / bisection loop for the reverse sweep (measured on the bench batches: -25 % with hold 4,
    // bit-identical results) -- where it exists (below) and only behind the gate of flatLoopStatus: validated toolchain and
    // a canary on this device --, the nested loops for the forward sweep (which does not gain)
@@ -1511,120 +1593,66 @@ static void launchSweep(batotp_batch *b, SweepArgs &a)
       // Only the form the canary of flatLoopStatus compares: 8 lanes per path in k_sweep8.  With 2 or 4 lanes per path, or with
       // k_sweep's own flat instantiation selected (batotp_hip_set_flat_form 0), the automatic choice keeps the nested loops --
       // an explicit batotp_hip_set_sweep_hold remains the developer's switch for those.
-      const bool candidate = G == 8 && featureLevel(b) <= 0 && uni && b->ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
+      const bool candidate = lanes == 8 && p.feat <= 0 && p.uni && ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
       hold = -1;
-      if (candidate && flatLoopStatus(b->ctx) == 1) hold = a.dir == -1 ? 4 : 8;
+      if (candidate && flatLoopStatus(b->ctx) == 1) hold = dir == -1 ? 4 : 8;
    }
    if (hold > 8) hold = 8;
-   a.hold = hold;
+   p.hold = hold;
    // The flat loop exists for the 8-lane layout of the velocity / acceleration-only problems (FEAT <= 0) on uniform knot
    // sites and nowhere else: the instantiation with the serial torque branch gave hold-dependent results on stalled paths
    // with this toolchain (ROCm 7.2.0 hipcc, clang 22; DESIGN.md 4, tools/experiments/), so problems with torque or
    // Cartesian limits always run the nested loops, and so do paths with uploaded (non-uniform) sites.
-   const bool flat = (G == 8 || G == 4 || G == 2) && hold >= 0 && featureLevel(b) <= 0 && uni;
-   b->lastLanes[a.dir == -1 ? 0 : 1] = G; b->lastPpw[a.dir == -1 ? 0 : 1] = ppw; b->lastHold[a.dir == -1 ? 0 : 1] = flat ? hold : -1;
+   p.flat = (lanes == 8 || lanes == 4 || lanes == 2) && hold >= 0 && p.feat <= 0 && p.uni;
    // the flat loop of the 8-lane layout written for the instruction count (sweep8.hip.h); 32-bit step counters
-   const bool form8 = flat && (G == 8 || G == 4) && b->ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
-   b->lastForm8[a.dir == -1 ? 0 : 1] = form8;
-#define LAUNCH_K4(F)                                                                           \
-   do {                                                                                        \
-      if (form8 && F <= 0)                                                                     \
-      {                                                                                        \
-         constexpr int F8 = F <= 0 ? F : 0, G8 = G == 4 ? 4 : 8;                               \
-         if (a.dir == 1) hipLaunchKernelGGL((k_sweep8<G8, F8, 1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);  \
-         else hipLaunchKernelGGL((k_sweep8<G8, F8, -1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);    \
-      }                                                                                        \
-      else if (flat) hipLaunchKernelGGL((k_sweep<G, F, true, ((G == 8 || G == 4 || G == 2) && F <= 0)>), dim3(grid), dim3(K4_BLOCK), 0, st, a);  \
-      else if (uni) hipLaunchKernelGGL((k_sweep<G, F, true>), dim3(grid), dim3(K4_BLOCK), 0, st, a);      \
-      else hipLaunchKernelGGL((k_sweep<G, F, false>), dim3(grid), dim3(K4_BLOCK), 0, st, a);        \
-   } while (0)
-   switch (featureLevel(b))
-   {
-   case -1: LAUNCH_K4(-1); break;
-   case 0: LAUNCH_K4(0); break;
-   case 1: LAUNCH_K4(1); break;
-   case 2: LAUNCH_K4(2); break;
-   default: LAUNCH_K4(3); break;
-   }
-#undef LAUNCH_K4
+   p.form8 = p.flat && (lanes == 8 || lanes == 4) && ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
+   return p;
 }
 
-// the one-path-per-wavefront kernel of sweep1.hip.h: joint velocity / acceleration limits only, uniform knot sites
-static bool sweep1Applies(const batotp_batch *b)
+template <int G>
+static void launchSweep(hipStream_t st, const SweepPlan &p, const SweepArgs &a)
 {
-   // every constraint family except the torque limits of a parallel mechanism that is still parallel (the cable robot without
-   // isPar2Ser: an LU solve per joint and limit); uniform knot sites
-   if (featureLevel(b) > 2) return false;
-   for (int p = 0; p < b->B; ++p)
-      if (!b->pinfo[p].uniform) return false;
-   return true;
+   const unsigned waves = (unsigned)((a.B + p.ppw - 1) / p.ppw);
+   const unsigned grid = (waves + (K4_BLOCK / 64) - 1) / (K4_BLOCK / 64);
+   withFeature(p.feat, [&](auto f) {
+      constexpr int F = decltype(f)::value;
+      if (p.form8 && F <= 0)
+      {
+         constexpr int F8 = F <= 0 ? F : 0, G8 = G == 4 ? 4 : 8;
+         if (a.dir == 1) hipLaunchKernelGGL((k_sweep8<G8, F8, 1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
+         else hipLaunchKernelGGL((k_sweep8<G8, F8, -1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
+      }
+      else if (p.flat) hipLaunchKernelGGL((k_sweep<G, F, true, ((G == 8 || G == 4 || G == 2) && F <= 0)>), dim3(grid), dim3(K4_BLOCK), 0, st, a);
+      else if (p.uni) hipLaunchKernelGGL((k_sweep<G, F, true>), dim3(grid), dim3(K4_BLOCK), 0, st, a);
+      else hipLaunchKernelGGL((k_sweep<G, F, false>), dim3(grid), dim3(K4_BLOCK), 0, st, a);
+   });
 }
 
-static void launchSweep1(batotp_batch *b, SweepArgs &a)
+// the one-path-per-wavefront kernel of sweep1.hip.h (or two: the cable robot in serial form with every channel as pairs, and the compact
+// velocity / acceleration-only layout)
+static void launchSweep1(hipStream_t st, const SweepPlan &p, const SweepArgs &a, bool pairsAll)
 {
-   a.ppw = 1; a.hold = -1; a.touch = 0; a.ff = b->ctx->fastForward; a.holdc = 0;
-   hipStream_t st = b->ctx->stream;
-   const bool cableLines = featureLevel(b) == 2 && (b->P.flags & BATOTP_F_PARALLEL) != 0 && b->pairsAll;
-   // Two paths per wavefront (k_sweep1's NP = 2; the cable robot in serial form with every channel as pairs): where one path per
-   // wavefront would leave wavefronts queueing for the two slots per SIMD the kernel's registers allow, or where the caller asks
-   // for it (batotp_hip_set_paths_per_wave(ctx, 2) with 64 lanes per path).  Measured on BASELINE config 5 (N = 2e5, reverse +
-   // forward ms; profiles/r05_h_*): up to 2048 paths every path has a resident wavefront either way and the sweeps last as long as
-   // the slowest path -- 1147 + 1326 with one path per wavefront, 1238 + 1474 with two (a wavefront that serves two paths is 8-11 %
-   // slower); 3072 paths 1613 + 1496 against 1244 + 1479; 4096 paths 2159 + 2033 against 1228 + 1479.  The crossover is at ~2300.
-   const int want = b->ctx->pathsPerWave;
-   // ... and the compact velocity / acceleration-only layout (round 5; the batch sizes between the one-path kernel and k_sweep8)
-   const bool compactVA = featureLevel(b) == -1;
-   // (a two-path wavefront of this family is 20 % slower in the reverse sweep and as fast as a one-path wavefront in the forward
-   //  sweep: 2048 paths 713 / 513 against 596 / 515 ms; one-path wavefronts queue beyond 2048 paths: 3072 paths 775 / 829 ms
-   //  against 901 / 646)
-   const bool two = (cableLines && (want == 2 || (want <= 0 && b->B > 2304))) ||
-                    (compactVA && (want == 2 || (want <= 0 && b->B > (a.dir == -1 ? 3500 : 2304))));
-   a.ppw = two ? 2 : 1;
-   b->lastLanes[a.dir == -1 ? 0 : 1] = 64; b->lastPpw[a.dir == -1 ? 0 : 1] = a.ppw; b->lastHold[a.dir == -1 ? 0 : 1] = -1;
-   const unsigned perBlock = (unsigned)(S1_BLOCK / 64) * (unsigned)a.ppw;
-   const unsigned grid = ((unsigned)b->B + perBlock - 1) / perBlock;
-   if (two && cableLines)
+   const unsigned perBlock = (unsigned)(S1_BLOCK / 64) * (unsigned)p.ppw;
+   const unsigned grid = ((unsigned)a.B + perBlock - 1) / perBlock;
+   // k_sweep1<F, dir, FF, PAIRS, NP>; PAIRS: the batch keeps all its channels as pairs
+   auto launch = [&](auto F, auto FF, auto PAIRS, auto NP) {
+      if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<F(), 1, FF(), PAIRS(), NP()>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
+      else hipLaunchKernelGGL((k_sweep1<F(), -1, FF(), PAIRS(), NP()>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
+   };
+   auto onePath = [&](auto F, auto FF) {
+      if (pairsAll) launch(F, FF, std::true_type(), Int<1>());
+      else launch(F, FF, std::false_type(), Int<1>());
+   };
+   if (p.ppw == 2)
    {
-      if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<2, 1, 0, true, 2>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-      else hipLaunchKernelGGL((k_sweep1<2, -1, 0, true, 2>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-      return;
+      if (p.feat == 2) launch(Int<2>(), Int<0>(), std::true_type(), Int<2>());
+      else launch(Int<-1>(), Int<0>(), std::false_type(), Int<2>());
    }
-   if (two)
-   {
-      if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<-1, 1, 0, false, 2>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-      else hipLaunchKernelGGL((k_sweep1<-1, -1, 0, false, 2>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-      return;
-   }
-   // (the last template argument: the batch keeps all its channels as pairs)
-#define LAUNCH_S1(F, FFORM)                                                                                              \
-   do {                                                                                                                 \
-      if (b->pairsAll)                                                                                                  \
-      {                                                                                                                 \
-         if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<F, 1, FFORM, true>), dim3(grid), dim3(S1_BLOCK), 0, st, a);       \
-         else hipLaunchKernelGGL((k_sweep1<F, -1, FFORM, true>), dim3(grid), dim3(S1_BLOCK), 0, st, a);                 \
-      }                                                                                                                 \
-      else                                                                                                              \
-      {                                                                                                                 \
-         if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<F, 1, FFORM, false>), dim3(grid), dim3(S1_BLOCK), 0, st, a);      \
-         else hipLaunchKernelGGL((k_sweep1<F, -1, FFORM, false>), dim3(grid), dim3(S1_BLOCK), 0, st, a);                \
-      }                                                                                                                 \
-   } while (0)
-   if (featureLevel(b) == 2)
-   {
-      // the fast-forward of the bisection in the form that fits the mechanism: a parallel robot converted to serial form has
-      // a3 = 0 (tension bounds are lines in sdot^2), a serial chain has friction (bounds quadratic in sdot)
-      const bool lines = (b->P.flags & BATOTP_F_PARALLEL) != 0;
-      if (lines) LAUNCH_S1(2, 0);
-      else LAUNCH_S1(2, 1);
-   }
-   else if (featureLevel(b) == 1) LAUNCH_S1(1, 0);
-   else if (b->compact && !b->pairsAll)
-   {
-      if (a.dir == 1) hipLaunchKernelGGL((k_sweep1<-1, 1>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-      else hipLaunchKernelGGL((k_sweep1<-1, -1>), dim3(grid), dim3(S1_BLOCK), 0, st, a);
-   }
-   else LAUNCH_S1(0, 0);
-#undef LAUNCH_S1
+   else if (p.feat == 2 && p.ff1 == 0) onePath(Int<2>(), Int<0>());
+   else if (p.feat == 2) onePath(Int<2>(), Int<1>());
+   else if (p.feat == 1) onePath(Int<1>(), Int<0>());
+   else if (p.feat == -1) launch(Int<-1>(), Int<0>(), std::false_type(), Int<1>());
+   else onePath(Int<0>(), Int<0>());
 }
 
 extern "C" int batotp_hip_sweep(batotp_batch *b, int32_t dir)
@@ -1638,54 +1666,29 @@ extern "C" int batotp_hip_sweep(batotp_batch *b, int32_t dir)
    b->mvcValid = false; // BATOTP_F_MVC_IN_CURVES: the sweep writes over the pointwise values
    SweepArgs a;
    a.P = b->P; a.dP = b->dP; a.pinfo = b->dPinfo; a.sC = b->dSC; a.coef = b->dCoef; a.km = b->compact ? b->dKM : nullptr; // (a zero-size allocation is not a null pointer: the kernels of the row layouts take a non-null km for "all channels as pairs")
-   a.rev = b->dRev; a.fwd = b->dFwd; a.res = b->dRes; a.sink = b->dSink; a.prof = b->dMvc; a.cap = b->cap; a.B = b->B; a.dir = dir; a.ppw = 1;
+   a.rev = b->dRev; a.fwd = b->dFwd; a.res = b->dRes; a.sink = b->dSink; a.prof = b->dMvc; a.cap = b->cap; a.B = b->B; a.dir = dir;
    a.order = b->ctx->pathOrder ? b->dOrder : nullptr;
 #ifdef S8_PROFILE
    a.prof = b->dProf;
    hipMemsetAsync(b->dProf, 0, sizeof(double) * ((size_t)b->B * 16 + 16), b->ctx->stream);
 #endif
    const int which = dir == -1 ? 3 : 4;
-   int lanes = b->ctx->sweepGroup;
-   if (lanes == 0)
-   {
-      // automatic: while the batch cannot fill the 8-lane layout anyway (<= 4 paths per SIMD), give a
-      // path 16 lanes and split the interval bounds over the two halves (fewer instructions per check)
-      // automatic (measured on UR6, N = 100k): up to ~2k paths the batch is latency-bound and the
-      // 32-lane layout (four bisection candidates per pass) wins; beyond that the 8-lane layout, which
-      // packs more paths per wavefront, has the higher throughput
-      lanes = (b->B <= (a.dir == -1 ? 2048 : 1024)) ? 32 : 8;
-      // ... and where every path has a wavefront to itself anyway, the kernel written for that case (sweep1.hip.h).  It also
-      // wins for a while beyond that, with its wavefronts queueing for the two slots per SIMD its registers leave: the 8-lane
-      // layout at 2-4 paths per wavefront is latency-bound and slower (GEN7DOF, N = 5e4, reverse: 3072 paths 944 vs 1882 ms,
-      // 6144 paths 1784 vs 2024, 8192 paths 2328 vs 2137; forward: 3072 paths 923 vs 981, 4096 paths 1118 vs 1031; UR6 alike)
-      // (round 4, against k_sweep8 instead of k_sweep -- N = 5e4, reverse / forward ms: 2048 paths 594 / 516 vs 1117 / 687, 4096 paths
-      //  1051 / 1008 vs 1231 / 738: the reverse crossover moved from ~6000 to ~4900 paths, the forward one stays near 3000)
-      if (sweep1Applies(b) && b->B <= (a.dir == -1 ? 4608 : 3072)) lanes = 64;
-      // (round 5, compact velocity / acceleration-only batches: with TWO paths per wavefront the one-path kernel keeps its lead over
-      //  the 8-lane layout up to ~7600 paths in the reverse and ~5000 in the forward sweep -- GEN7DOF, N = 5e4, reverse / forward ms,
-      //  one path | two paths | 8 lanes: 4096 paths 1055 / 1004 | 902 / 646 | 1345 / 738; 6144 paths 1460 / 1480 | 1152 / 1050 |
-      //  1460 / 868; 8192 paths 1905 / 1950 | 1588 / 1260 | 1505 / 868: profiles/r05_i_*; launchSweep1 picks one or two)
-      if (sweep1Applies(b) && featureLevel(b) == -1 && b->B <= (a.dir == -1 ? 7600 : 5000)) lanes = 64;
-   }
-   if (b->pairsAll)
-   {
-      // rows exist in the LDS windows of the one-path-per-wavefront kernel only
-      if (!sweep1Applies(b)) { snprintf(g_err, sizeof(g_err), "pairs for all channels need uniform knot sites and constraints in serial form"); return BATOTP_ERR_STATE; }
-      lanes = 64;
-   }
-   if (lanes == 64 && !sweep1Applies(b)) lanes = 32; // a parallel mechanism's torque limits, uploaded sites: the general kernel
-   // the gate of the flat loop (its canary launches sweeps of its own) is settled before this sweep's timed region starts
-   if (b->ctx->sweepHold[dir == -1 ? 0 : 1] == -2 && (lanes == 8 || lanes == 4 || lanes == 2) && featureLevel(b) <= 0) (void)flatLoopStatus(b->ctx);
+   // (the plan settles the gate of the flat loop before this sweep's timed region starts)
+   const SweepPlan p = planSweep(b, dir);
+   if (p.lanes == 0) { snprintf(g_err, sizeof(g_err), "pairs for all channels need uniform knot sites and constraints in serial form"); return BATOTP_ERR_STATE; }
+   a.ppw = p.ppw; a.hold = p.hold; a.touch = p.touch; a.ff = p.ff; a.holdc = p.holdc;
+   b->lastPlan[dir == -1 ? 0 : 1] = p;
+   hipStream_t st = b->ctx->stream;
    evStart(b, which);
-   switch (lanes)
+   switch (p.lanes)
    {
-   case 64: launchSweep1(b, a); break;
-   case 32: launchSweep<32>(b, a); break;
-   case 1: launchSweep<1>(b, a); break;
-   case 16: launchSweep<16>(b, a); break;
-   case 4: launchSweep<4>(b, a); break;
-   case 2: launchSweep<2>(b, a); break;
-   default: launchSweep<8>(b, a); break;
+   case 64: launchSweep1(st, p, a, b->pairsAll); break;
+   case 32: launchSweep<32>(st, p, a); break;
+   case 1: launchSweep<1>(st, p, a); break;
+   case 16: launchSweep<16>(st, p, a); break;
+   case 4: launchSweep<4>(st, p, a); break;
+   case 2: launchSweep<2>(st, p, a); break;
+   default: launchSweep<8>(st, p, a); break;
    }
    evStop(b, which);
    HIP_TRY(hipGetLastError());

@@ -1179,11 +1179,7 @@ template <int G, int FEAT, bool UNI>
 __device__ __forceinline__ void eval_partials(Pt<G, FEAT, UNI> &t, int j)
 {
    update_cur_seg<UNI ? 0 : 1>(t.sC, t.sresC, t.n, t.sCur, t.segC, t.tauC, t.status);
-#ifndef BK_NO_ROWCACHE
    if (FEAT <= 0)
-#else
-   if (FEAT < 0)
-#endif
    {
       eval_partials_cached(t, j);
       return;
@@ -1940,10 +1936,7 @@ __device__ __forceinline__ int touch_curve_ahead(const Pt<G, FEAT, UNI> &t, int 
 // A workgroup is 4 wavefronts (one per SIMD of a CU): with one-wavefront workgroups the dispatcher was
 // observed to stack several of them on the SIMDs of one CU while other CUs stayed empty.
 constexpr int K4_BLOCK = 256;
-#ifndef BK_SWEEP_WPE
-#define BK_SWEEP_WPE 2
-#endif
-// waves per SIMD the register allocation of the narrow (FEAT <= 1) sweep kernels is tuned for
+constexpr int BK_SWEEP_WPE = 2; // waves per SIMD the register allocation of the narrow (FEAT <= 1) sweep kernels is tuned for
 // FLAT: the stage loop and the bisection loop are one loop in which every path of the wavefront is either
 // waiting for its next stage or inside a constraint check (see the comment at the loop).
 template <int G, int FEAT, bool UNI, bool FLAT = false>

@@ -11,7 +11,7 @@
 //     literals (no selects on the stage number, no table look-ups), one joint per lane without per-lane loops, the constraint
 //     families that are off compiled out, the stage's spline row and the knot sites of its segment kept in registers,
 //     conditions on path-level values as scalar branches (S1_UNI), and the bisection -- a quarter of the stages need it --
-//     either fast-forwarded (S1_PREDICT) or evaluating four candidates of the reference's (deterministic) candidate sequence
+//     either fast-forwarded (the certificate below) or evaluating four candidates of the reference's (deterministic) candidate sequence
 //     per pass, as the 32-lane layout of k_sweep does;
 //   * lanes: lane = slot * 8 + joint, 4 candidate slots x 8 joint lanes; the other 32 lanes of the wavefront exit.
 #pragma once
@@ -43,10 +43,7 @@ __device__ __forceinline__ bool ratio_lt_uniform(double num, double den, double 
 // 1: a violated first check of a problem whose constraints are lines in sdot^2 goes through the CERTIFIED FAST-FORWARD of the
 // bisection first (see accelPt): the speed at which the sddot intervals stop intersecting has a closed form there, and the
 // iterations of the reference's loop whose outcome is certain given the check's rounding-error bound are taken without their
-// checks (batotp_hip_set_fast_forward switches it off at run time; 0 here compiles it out)
-#ifndef S1_PREDICT
-#define S1_PREDICT 1
-#endif
+// checks (batotp_hip_set_fast_forward switches it off at run time; against the four-candidate replay alone: profiles/r03_b_*)
 // tableau of ba.cpp:58-63 as a table: entry [6*k + m] = _B[k][m] (stage m + 1 combines the stage values k = 0..m)
 __constant__ double c_s1B[36] = {BK_B00, BK_B01, BK_B02, BK_B03, BK_B04, BK_B05,
                                  0, BK_B11, BK_B12, BK_B13, BK_B14, BK_B15,
@@ -72,11 +69,10 @@ __constant__ double c_s1B[36] = {BK_B00, BK_B01, BK_B02, BK_B03, BK_B04, BK_B05,
 constexpr int S1_BLOCK = 256;
 constexpr int S1_WK = 64;   // knots per spline window (compact splines: 64 knots x 8 joint slots x 16 B = 8 KB per path)
 constexpr int S1_WM = 256;  // points per reverse-curve window (4 KB per path)
-#ifndef S1_WR_BYTES
-#define S1_WR_BYTES 12288   // coefficient rows (FEAT >= 0): LDS bytes per path for the window of consecutive rows (C x 32 B each: 21 rows of the
-                            // cable robot's 18 channels, 10 of the 7-DOF arm's 38).  With the reverse-curve window of the forward sweep a
-                            // block of four paths takes 64.4 KB: two blocks per CU (two wavefronts per SIMD) still fit the 160 KB
-#endif
+// coefficient rows (FEAT >= 0): LDS bytes per path for the window of consecutive rows (C x 32 B each: 21 rows of the cable robot's 18
+// channels, 10 of the 7-DOF arm's 38).  With the reverse-curve window of the forward sweep a block of four paths takes 64.4 KB: two
+// blocks per CU (two wavefronts per SIMD) still fit the 160 KB
+constexpr int S1_WR_BYTES = 12288;
 
 // FEAT: -1 = compact splines ((value, second derivative) pairs), 0 = coefficient rows, 1 = coefficient rows + the Cartesian
 // speed / acceleration limits (ba.cpp:1225-1229, 1423-1439, 1535-1579), 2 = those + torque limits of a
@@ -114,7 +110,7 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
    static_assert(!PAIRS || FEAT >= 0, "FEAT -1 reads its joint pairs through winK");
    // rows through an LDS window: always when the batch keeps pairs only; for rows in HBM where it measured faster (the cable robot's
    // sweeps 4-6 %, not the 7-DOF arm's, whose cursor needs a new row every other step)
-   constexpr bool ROWWIN = FEAT >= 0 && S1_WR_BYTES > 0 && (PAIRS || (FEAT == 2 && FF == 0));
+   constexpr bool ROWWIN = FEAT >= 0 && (PAIRS || (FEAT == 2 && FF == 0));
    __shared__ double2 winRAll[ROWWIN ? NW : 1][ROWWIN ? WRB / 16 : 1];
    stage_limits(a.dP, lim);
    const int lane = threadIdx.x & 63;
@@ -637,7 +633,6 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
       };
       // the first check (violated) is the loop's first iteration; the passes below start with its successor
       bool over = S1_FIRST((int)iterate(true)) != 0;
-#if S1_PREDICT
       // where it applies: the check consists of constraints that are LINES in x = sdot^2 -- joint acceleration limits, and
       // the torque limits of a mechanism whose a3 (the term in sdot) vanishes identically, i.e. the cable robot in serial form
       // (robot.cpp:487-517: a3 = 0 at every knot, so its spline is 0 and tmp1 of ba.cpp:1497 is a4 exactly); no Cartesian
@@ -645,16 +640,10 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
       // at most 4 joints.
       // (not in the forward kernel of a pair batch: it is held to 256 registers -- two paths per SIMD --, the forward sweep bisects in
       //  0.6 % of its stages, and without the block 22 instead of 35 registers spill: cfg 5 forward 3194 -> 3021 ms)
-#ifndef S1_FWD_PAIRS_FF
-#define S1_FWD_PAIRS_FF 0
-#endif
-#ifndef S1_FAIL_FF
-#define S1_FAIL_FF 1   // the certificate of a stage whose bisection cannot succeed (0: A/B, the kernels of round 5)
-#endif
-      constexpr bool FF0 = FF == 0 && (S1_FWD_PAIRS_FF || !(PAIRS && DIR == 1));
+      constexpr bool FF0 = FF == 0 && !(PAIRS && DIR == 1);
       // (round 6) the certificate of a stage that CANNOT succeed -- see below -- is a small part of the block and is compiled into every
       // instantiation of this form, the forward kernel of a pair batch included
-      constexpr bool FFAIL0 = FF == 0 && (S1_FAIL_FF != 0);
+      constexpr bool FFAIL0 = FF == 0;
       bool ffApplies = (FF0 || FFAIL0) && a.ff && !over && !cartAccOn && (FEAT == 2 || accOn);
       if (FEAT == 2) ffApplies = ffApplies && nJ <= 4 && !S1_BALLOT(jv && !(a3pt == 0.0));
       if ((FF0 || FFAIL0) && ffApplies)
@@ -992,7 +981,6 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
             }
          }
       }
-#endif
       while (!over)
       {
 #ifdef BK_PROFILE_SECTIONS

@@ -38,45 +38,15 @@ namespace bk
 {
 
 constexpr int S8_BLOCK = 256;
-__device__ __forceinline__ bool s8_div_window_fwd(double x) { return sdiv_window(x); }
 // "does any active lane ...": the i1 ballot intrinsic (HIP's __ballot goes through an integer compare: a v_cndmask + v_cmp per use)
 #define S8_ANY(x) (__builtin_amdgcn_ballot_w64(x) != 0)
 #define S8_RARE(x) __builtin_expect(S8_ANY(x), 0) // a guard whose block is off the straight-line code
-#ifndef S8_TAB_FAST
-#define S8_TAB_FAST 1   // tableau combination without selects while every stage value is finite
-#endif
-#ifndef S8_LDS_STAGES
-#define S8_LDS_STAGES 1 // the stage values (v_k, w_k), k = 1..5, of a path live in LDS instead of registers + 20 selects per stage
-#endif
-#ifndef S8_WALK_PRECHECK
-#define S8_WALK_PRECHECK 1 // skip the knot-cursor walk when every path is still inside its segment
-#endif
-#ifndef S8_PREFETCH
-#define S8_PREFETCH 1   // the knot the cursor will need next is loaded one segment change ahead (compact pairs).  (The same for the next
-                        // point of the reverse curve in the forward sweep measured 5 % slower -- 440 against 419 ms -- and is not done.)
-#endif
-#ifndef S8_TAU_RCP
-#define S8_TAU_RCP 0 // tau = (sCur - sSeg) / (sNext - sSeg) and the reverse-curve tau of the forward sweep through the refined reciprocal of
-                     // their segment's width (device_math.h: sdiv_rcp / sdiv_by, the bits of `/` inside the window and for a numerator of
-                     // +0), kept while the cursor stays on the segment: 3 instead of ~30 instructions per stage on the dependent chain.
-                     // Round 5 gave the literal quotient (an operand outside the window) a wavefront-uniform guard of its own and measured
-                     // 5-7 % SLOWER; round 6 let it share the guard of the segment change, which a third of the prologues enter anyway:
-                     // SLOWER again (reduced batch, same box: reverse 626 against 601 ms, forward 417 against 386 ms; profiles/r06_b_*).
-                     // The division is not what these wavefronts wait for.  Kept as an option, bit-identical.
-#endif
-#ifndef S8_SPEC_MID
-#define S8_SPEC_MID 0  // s8_certify's bisection replay forms both possible next candidates beside the test: a shorter dependent chain, four more
-                       // fp64 instructions per iteration -- bit-identical, reverse sweep 2.3 % SLOWER (profiles/r06_p_*): the block is issue-bound
-#endif
-#ifndef S8_FF
-#define S8_FF 1      // the certified fast-forward of the bisection (s8_certify), both directions (batotp_hip_set_fast_forward: bit 0 forward, bit 1 reverse)
-#endif
-#ifndef S8_FF_REV
-#define S8_FF_REV 1  // 0: the reverse kernel carries no certificate code at all (the kernel of rounds 4 and 5, for A/B runs)
-#endif
-#ifndef S8_CERT_PHASE
-#define S8_CERT_PHASE 1 // reverse sweep: the certificate as a phase of its own, served in batches (0: in the check block, per arriving path)
-#endif
+// Measured and settled, no longer switches (DESIGN.md 4 has the numbers):
+//   kept: tableau combination without selects, stage values in LDS, walk pre-check, knot prefetch (round 4, profiles/r04_a_*)
+//   kept: the certified fast-forward in both directions (profiles/r04_j_*), in the reverse sweep as a phase of its own (profiles/r06_a_*)
+//   removed: the cursor quotients through cached reciprocals, 4-7 % slower (profiles/r05_e_*, r06_a_*)
+//   removed: both next candidates beside the test in the certificate's replay, 2.3 % slower (profiles/r06_p_*)
+// (Prefetching the next point of the reverse curve in the forward sweep measured 5 % slower -- 440 against 419 ms -- and is not done.)
 
 // (num / den) < thr as ratio_lt (kernels.hip.h) decides it, in two parts: the product form, and whether it was decisive
 __device__ __forceinline__ bool s8_ratio_lt_fast(double num, double den, double thr, bool &decided)
@@ -103,26 +73,18 @@ __device__ __forceinline__ void s8_ratio_lt_pair(double num1, double num2, doubl
    dec2 = ok & (lt2 | (num2 > den * (T2 * (1.0 + 1e-14))));
 }
 
-// numerator of a quotient by a cached reciprocal: inside the window, or +0 (0 * r = +0, the remainder fma(-den, +0, +0) = +0, the result
-// fma(+0, r, +0) = +0 = (+0) / den for the positive divisors this is used with; a numerator of -0 would come out as +0 and takes the
-// literal form)
-__device__ __forceinline__ bool s8_num_ok(double x) { return s8_div_window_fwd(x) | (__double_as_longlong(x) == 0ll); }
 // (the shared refined reciprocal of theta' -- sdiv_window / sdiv_rcp / sdiv_by -- lives in device_math.h.  In k_sweep1, the
 // one-path-per-wavefront kernel, the same technique measured 3-10 % SLOWER -- cfg 4: 961 against 874 ms -- and is not used there:
 // its window tests and ballot guards cost a lone wavefront more than the shorter quotients save; profiles/r04_b_*)
-constexpr double S8_DIV_LO = SDIV_LO, S8_DIV_HI = SDIV_HI;
-__device__ __forceinline__ bool s8_div_window(double x) { return sdiv_window(x); }
-__device__ __forceinline__ double s8_rcp_refined(double den) { return sdiv_rcp(den); }
-__device__ __forceinline__ double s8_div_by(double num, double den, double r) { return sdiv_by(num, den, r); }
 
 // known-answer test of the shared-reciprocal division against `/` (batotp_hip_fp64_kat)
 __global__ void k_kat_sdiv(int64_t n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ q, int *__restrict__ inWindow)
 {
    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
    if (i >= n) return;
-   const bool ok = s8_div_window(a[i]) & s8_div_window(b[i]);
+   const bool ok = sdiv_window(a[i]) & sdiv_window(b[i]);
    inWindow[i] = ok ? 1 : 0;
-   q[i] = ok ? s8_div_by(a[i], b[i], s8_rcp_refined(b[i])) : a[i] / b[i];
+   q[i] = ok ? sdiv_by(a[i], b[i], sdiv_rcp(b[i])) : a[i] / b[i];
 }
 
 // ---- CERTIFIED FAST-FORWARD of the bisection on the 8 lanes of a path (the certificate of k_sweep1, sweep1.hip.h: its derivation
@@ -252,24 +214,13 @@ __device__ __forceinline__ void s8_certify(bool jOn, double thD, double thD2, do
       for (;;)
       {
          const double c = sdotTry, d = c * c - xThr;
-#if S8_SPEC_MID
-         // both possible next candidates, computed beside the test instead of behind it (the same sums as ba.cpp:1320 forms after the
-         // update: .5 * (c + sdotL) when c becomes sdotH, .5 * (sdotH + c) when it becomes sdotL; a lane that has stopped keeps c, which
-         // IS .5 * (sdotH + sdotL) by the invariant): the dependent chain of an iteration is square - subtract - compare - select
-         // instead of square - subtract - compare - select - add - halve
-         const double nextV = .5 * (c + sdotL), nextG = .5 * (sdotH + c);
-#endif
          const bool viol = d > 0.0;
          const bool goesOn = viol | (fabs(c - sdotL) > convThr * c);
          more = more & (fabs(d) > bandThr) & goesOn & (it < 90);
          if (!S8_ANY(more)) break;
          sdotH = (more & viol) ? c : sdotH;
          sdotL = (more & !viol) ? c : sdotL;
-#if S8_SPEC_MID
-         sdotTry = more ? (viol ? nextV : nextG) : c;
-#else
          sdotTry = .5 * (sdotH + sdotL);
-#endif
          it += more ? 1 : 0;
       }
       sdotGood = bisect ? sdotL : sdotGood;
@@ -287,9 +238,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    __shared__ double lim[6][8];
    __shared__ double rk[7][6];                 // rk[st][k] = weight of stage value k in stage st (column st-1 of ba.cpp:58-63), 0 for k >= st
    __shared__ double2 pts[S8_BLOCK / G][4];    // curve points of a path waiting for their 64-byte store
-#if S8_LDS_STAGES
    __shared__ double2 vw[S8_BLOCK / G][8];     // (v_k, w_k) of stage k = 1..5 of every path; slot 0 and 7: writes that must not land
-#endif
    if (threadIdx.x < 42)
    {
       const double tab[42] = {0, 0, 0, 0, 0, 0,
@@ -315,10 +264,8 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    const int n = (int)pi.n;
    const int64_t cap = a.cap;
    double2 *mypts = pts[threadIdx.x / G];
-#if S8_LDS_STAGES
    double2 *myvw = vw[threadIdx.x / G];
    for (int k = j; k < 8; k += G) myvw[k] = make_double2(0.0, 0.0);
-#endif
 
    // bootstrap (ba.cpp:1021-1041) through the general kernel's device functions; the loop below carries its own state
    Pt<G, FEAT, true> t;
@@ -374,7 +321,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    double vmax[PER], amax[PER];
    // this lane's coefficients on the cursor's segment: c1, 2 c2, 3 c3, 6 c3 (the products the reference forms first:
    // (3*c3)*tau2, (2*c2)*tau, (6*c3)*tau, ba.cpp:1358-1360); theta', theta'' of the last evaluation point; the refined
-   // reciprocal of theta' (s8_rcp_refined) and whether theta' lies in the window in which it may be used
+   // reciprocal of theta' (sdiv_rcp) and whether theta' lies in the window in which it may be used
    double c1[PER], c2x2[PER], c3x3[PER], c3x6[PER], thD[PER], thD2[PER], rD[PER];
    double sa[PER]; // sgn(theta') * amax of ba.cpp:1526-1531 where theta' != 0: amax with the sign of theta' (1.0 * amax and -1.0 * amax are exact)
    bool rOk[PER];
@@ -387,8 +334,8 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
       c1[q] = jOn[q] ? t.rowTh[q].c1 : 0.0; c2x2[q] = jOn[q] ? 2 * t.rowTh[q].c2 : 0.0;
       c3x3[q] = jOn[q] ? 3 * t.rowTh[q].c3 : 0.0; c3x6[q] = jOn[q] ? 6 * t.rowTh[q].c3 : 0.0;
       thD[q] = t.thD[q]; thD2[q] = t.thD2[q];
-      rOk[q] = s8_div_window(thD[q]);
-      rD[q] = s8_rcp_refined(thD[q]);
+      rOk[q] = sdiv_window(thD[q]);
+      rD[q] = sdiv_rcp(thD[q]);
       sa[q] = (thD[q] < 0.0) ? -amax[q] : amax[q];
    }
    const bool accOn = (t.flags & BATOTP_F_JNT_ACC_ON) != 0;
@@ -401,7 +348,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    const double *__restrict__ coef = t.coef;
    const int rowStride = t.C * 4;
    int seg = t.segC, rowSeg = t.rowSeg;
-   // S8_PREFETCH (compact pairs): the knot on the side the cursor moves to (reverse: knot rowSeg, forward: knot rowSeg + 1)
+   // knot prefetch (compact pairs): the knot on the side the cursor moves to (reverse: knot rowSeg, forward: knot rowSeg + 1)
    // and the one beyond it, loaded when the cursor entered the current segment -- a segment change one step further then
    // forms its coefficients from registers and issues the load for the change after it
    double2 kEdge[PER], kPre[PER];
@@ -409,15 +356,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
 #pragma unroll
    for (int q = 0; q < PER; ++q) { kEdge[q] = make_double2(0, 0); kPre[q] = make_double2(0, 0); }
    double sSeg = sres * (double)seg, sNext = sres * (double)(seg + 1); // sites of the cursor's segment
-#if S8_TAU_RCP
-   double rSeg = s8_rcp_refined(sNext - sSeg); // refined reciprocal of the segment's width (renewed when the walk ran)
-   bool segOk = s8_div_window(sNext - sSeg) & (sNext - sSeg > 0.0);
-   double rM = 0;   // the same for the reverse-curve segment of the forward sweep
-   bool mOk = false;
-   // forward sweep: what the literal form of evalsdot's quotient needs when it is redone behind the guard of the segment change
-   double numM = 0, denM = 1, vPre = 0;
-   bool fastM = true;
-#endif
    // reverse-curve cursor (forward sweep): segment and its two points
    int segM = 0;
    double mS0 = 0, mD0 = 0, mS1 = 0, mD1 = 0;
@@ -426,9 +364,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
       segM = t.segMVC;
       const double2 qa = mvc[segM], qb = mvc[segM + 1];
       mS0 = qa.x; mD0 = qa.y; mS1 = qb.x; mD1 = qb.y;
-#if S8_TAU_RCP
-      rM = s8_rcp_refined(mS1 - mS0); mOk = s8_div_window(mS1 - mS0) & (mS1 - mS0 > 0.0);
-#endif
    }
    unsigned status = t.status;
    int nfail = t.nfail;
@@ -462,7 +397,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    constexpr int PH_FIRST = 0, PH_ENDED = 1, PH_CHECK = 2, PH_DEAD = 3, PH_CERT = 4;
    // reverse sweep: a path whose first check was violated waits in PH_CERT for the certificate block at the top of the loop, which
    // runs once holdC/8 of the live paths have gathered there (or nothing else can run in this pass)
-   constexpr bool CERT = (DIR == -1) && (PER == 1) && (S8_FF != 0) && (S8_FF_REV != 0) && (S8_CERT_PHASE != 0);
+   constexpr bool CERT = DIR == -1 && PER == 1;
    const int holdC = a.holdc;
    int phase = PH_ENDED;
    if (S8_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; phase = PH_DEAD; }
@@ -521,7 +456,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                phase = PH_FIRST;
                const double vN = sdotCur;
                wild |= !(fabs(vN) < kInf) | !(fabs(wN) < kInf);
-#if S8_LDS_STAGES
                // slot st keeps (vN, wN); a failed bisection leaves sddotArr[st] as it was (the w half goes to the spare slot 7);
                // stage 6 is kept in registers by the step end below (its writes go to the spare slot 7 as well)
                {
@@ -530,14 +464,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   *slotV = vN;
                   *slotW = wN;
                }
-#else
-               const int stW = stageFailed ? 0 : st; // a failed bisection leaves sddotArr[st] as it was
-               v1 = (st == 1) ? vN : v1; w1 = (stW == 1) ? wN : w1;
-               v2 = (st == 2) ? vN : v2; w2 = (stW == 2) ? wN : w2;
-               v3 = (st == 3) ? vN : v3; w3 = (stW == 3) ? wN : w3;
-               v4 = (st == 4) ? vN : v4; w4 = (stW == 4) ? wN : w4;
-               v5 = (st == 5) ? vN : v5; w5 = (stW == 5) ? wN : w5;
-#endif
                const bool stepEnd = (st == 6);
                st = stepEnd ? st : st + 1;
                if (S8_ANY(stepEnd))
@@ -596,12 +522,10 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                // ---- tableau combination, ba.cpp:1073-1085 ---------------------------------------------
                const double *bc = rk[st];
                double sdotT = 0, sddotT = 0;
-#if S8_LDS_STAGES
                {
                   const double2 q1 = myvw[1], q2 = myvw[2], q3 = myvw[3], q4 = myvw[4], q5 = myvw[5];
                   v1 = q1.x; w1 = q1.y; v2 = q2.x; w2 = q2.y; v3 = q3.x; w3 = q3.y; v4 = q4.x; w4 = q4.y; v5 = q5.x; w5 = q5.y;
                }
-#endif
                // Stage st adds the terms k < st only.  The weights of the others are +0 in the table, and adding their products
                // changes nothing as long as every stage value is finite (x + (+-0) = x: a partial sum starts as 0 + b0 v0 and
                // is therefore never -0); a path that ever kept a non-finite stage value (0 * inf = NaN) takes the literal form.
@@ -610,9 +534,9 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                // reciprocal (further down: `odd` is then a scalar condition)
                bool slowDiv = false;
 #pragma unroll
-               for (int q = 0; q < PER; ++q) slowDiv |= jOn[q] && fabs(thD[q]) > thrV && !(rOk[q] & s8_div_window(vmax[q]));
+               for (int q = 0; q < PER; ++q) slowDiv |= jOn[q] && fabs(thD[q]) > thrV && !(rOk[q] & sdiv_window(vmax[q]));
                const bool odd = S8_RARE(wild | slowDiv);
-               if (S8_TAB_FAST && !odd)
+               if (!odd)
                {
                   sdotT += bc[0] * v0; sddotT += bc[0] * w0;
                   sdotT += bc[1] * v1; sddotT += bc[1] * w1;
@@ -640,14 +564,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                {
                   // evalsdot, ba.cpp:1590-1607
 #include "sweep8_mvcwalk.inc"
-#if S8_TAU_RCP
-                  numM = sCur - mS0; denM = mS1 - mS0;
-                  fastM = mOk & s8_num_ok(numM);
-                  vPre = vN;
-                  const double tauM = s8_div_by(numM, denM, rM);   // (a lane with !fastM is redone behind the guard of the segment change)
-#else
                   const double tauM = (sCur - mS0) / (mS1 - mS0);
-#endif
                   const double sdotMVC = dmax(mD0 + tauM * (mD1 - mD0), sdotMin);
                   vN = (vN > sdotMVC) ? sdotMVC : vN;
                }
@@ -659,8 +576,8 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   for (int q = 0; q < PER; ++q)
                   {
                      const bool on = jOn[q] && fabs(thD[q]) > thrV;
-                     const bool fast = rOk[q] & s8_div_window(vmax[q]);
-                     const double qv = fabs(s8_div_by(vmax[q], thD[q], rD[q]));
+                     const bool fast = rOk[q] & sdiv_window(vmax[q]);
+                     const double qv = fabs(sdiv_by(vmax[q], thD[q], rD[q]));
                      lim1 = (on & fast) ? dmin(lim1, qv) : lim1;
                   }
                   if (odd)
@@ -669,7 +586,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                      for (int q = 0; q < PER; ++q)
                      {
                         const bool on = jOn[q] && fabs(thD[q]) > thrV;
-                        const bool fast = rOk[q] & s8_div_window(vmax[q]);
+                        const bool fast = rOk[q] & sdiv_window(vmax[q]);
                         if (on && !fast) lim1 = dmin(lim1, fabs(vmax[q] / thD[q]));
                      }
                   }
@@ -681,7 +598,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                lowFact = .01; sdotGood = 0; nGood = 0; sdotL = 0; sdotH = vN; sdotTry = vN; nIter = 0; stageFailed = false;
 
                // ---- evalSplinePartials, ba.cpp:1341-1413: updateCurSeg (ba.cpp:1617-1652) on the sites sres*k ----
-               if (!S8_WALK_PRECHECK || S8_ANY(!((sCur >= sSeg) & (sCur <= sNext))))
+               if (S8_ANY(!((sCur >= sSeg) & (sCur <= sNext))))
                {
                   S8_CNT(10, 1);
                   for (;;)
@@ -695,40 +612,11 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                      seg = mvUp ? seg + 1 : (mvDn ? seg - 1 : seg);
                      if (!S8_ANY(mvUp | mvDn)) break;
                   }
-#if S8_TAU_RCP
-                  rSeg = s8_rcp_refined(sNext - sSeg); segOk = s8_div_window(sNext - sSeg) & (sNext - sSeg > 0.0);
-#endif
                }
-#if S8_TAU_RCP
-               const double numT = sCur - sSeg, denT = sNext - sSeg;
-               const bool fastT = segOk & s8_num_ok(numT);
-               double tau = s8_div_by(numT, denT, rSeg);
-               const bool slowM = (DIR == 1) && !fastM;
-#else
                double tau = (sCur - sSeg) / (sNext - sSeg);
-               const bool fastT = true, slowM = false;
-#endif
                const bool chg = (seg != rowSeg);
-               // one guard for the segment change and for the quotients that need their literal form
-               if (S8_ANY(chg | !fastT | slowM))
+               if (S8_ANY(chg))
                {
-#if S8_TAU_RCP
-                  if (!fastT) tau = numT / denT;
-                  if (DIR == 1)
-                  {
-                     if (slowM)
-                     {
-                        // evalsdot and the rest of sdotLim once more with the literal quotient (ba.cpp:1590-1607, 1216-1229)
-                        const double tauM = numM / denM;
-                        const double sdotMVC = dmax(mD0 + tauM * (mD1 - mD0), sdotMin);
-                        double vR = (vPre > sdotMVC) ? sdotMVC : vPre;
-                        vR = dmin(vR, sdotCap);
-                        vR = dmax(vR, sdotMin);
-                        vR = dmin(vR, lim1);
-                        sdotCur = vR; sdotH = vR; sdotTry = vR;
-                     }
-                  }
-#endif
                   S8_CNT(9, 1);
                   if (chg)
                   {
@@ -738,9 +626,10 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                         if (FEAT < 0)
                         {
                            const unsigned at = (unsigned)(seg * nIn + jAt[q]);
+                           // (declared here, assigned in the blocks below: initialising them at their declaration swaps two register pairs of
+                           //  the validated build, profiles/refactor_code_object_identity.txt)
                            double2 kl, kr; // knots seg and seg + 1 of this joint
                            bool literal = false; // the knots are not the prefetched ones, or a sixth lies outside div6's window
-                           if (S8_PREFETCH)
                            {
                               // one segment further in the direction of the sweep: both knots are in registers
                               const bool hit = (DIR == 1) ? (preIdx == seg + 1) : (preIdx == seg);
@@ -748,7 +637,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                               kr = (DIR == 1) ? kPre[q] : kEdge[q];
                               literal = !hit;
                            }
-                           else { kl = km[at]; kr = km[at + nIn]; }
                            // emit_segment's formulas (spline.cpp:203-209); x / 6 as div6 computes it inside its window, and ONE
                            // wavefront-uniform guard for everything that is rare here (a missed prefetch, a sixth outside the window)
                            double solL = kl.y, solR = kr.y, yL = kl.x, yR = kr.x;
@@ -762,7 +650,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                            }
                            if (S8_RARE(literal))
                            {
-                              if (S8_PREFETCH)
                               {
                                  const bool hit = (DIR == 1) ? (preIdx == seg + 1) : (preIdx == seg);
                                  const double2 dl = km[at], dr = km[at + nIn];
@@ -773,7 +660,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                               c3 = div6(solR - solL);
                               sixthB = div6(solR + 2 * solL);
                            }
-                           if (S8_PREFETCH)
                            {
                               kEdge[q] = (DIR == 1) ? kr : kl;
                               int nxt = (DIR == 1) ? seg + 2 : seg - 1;
@@ -790,7 +676,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                            c1[q] = k.c1; c2x2[q] = 2 * k.c2; c3x3[q] = 3 * k.c3; c3x6[q] = 6 * k.c3;
                         }
                      }
-                     if (S8_PREFETCH && FEAT < 0)
+                     if (FEAT < 0)
                      {
                         const int nxt = (DIR == 1) ? seg + 2 : seg - 1;
                         preIdx = nxt < 0 ? (-(1 << 20)) : (nxt > lastSeg + 1 ? (-(1 << 20)) : nxt); // a clamped prefetch holds no usable knot
@@ -805,8 +691,8 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   {
                      thD[q] = (c3x3[q] * tau2 + c2x2[q] * tau + c1[q]) * vfact;
                      thD2[q] = (c3x6[q] * tau + c2x2[q]) * afact;
-                     rOk[q] = s8_div_window(thD[q]);
-                     rD[q] = s8_rcp_refined(thD[q]);
+                     rOk[q] = sdiv_window(thD[q]);
+                     rD[q] = sdiv_rcp(thD[q]);
                      sa[q] = (thD[q] < 0.0) ? -amax[q] : amax[q];
                   }
                }
@@ -845,9 +731,9 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                const bool slow = fabs(thD[q]) < thrV;
                const double vTerm = thD2[q] * sdotSQ;
                const double nH = sa[q] - vTerm, nL = -sa[q] - vTerm; // (theta' = 0 lies outside the window: the literal form below)
-               const bool fast = capOk & rOk[q] & s8_div_window(nH) & s8_div_window(nL);
-               const double qH = s8_div_by(nH, thD[q], rD[q]);
-               const double qL = s8_div_by(nL, thD[q], rD[q]);
+               const bool fast = capOk & rOk[q] & sdiv_window(nH) & sdiv_window(nL);
+               const double qH = sdiv_by(nH, thD[q], rD[q]);
+               const double qL = sdiv_by(nL, thD[q], rD[q]);
                const bool use = jOn[q] & !slow & fast;
                // inside the window both quotients are finite and the bound is not a NaN (capOk): the one-instruction min / max
                // returns what the compare-and-select form returns (device_math.h: up to the sign of a zero that nothing reads)
@@ -866,7 +752,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   const int svpt = sgn(thD[q]);
                   const double vTerm = thD2[q] * sdotSQ;
                   const double nH = svpt * amax[q] - vTerm, nL = -svpt * amax[q] - vTerm;
-                  const bool fast = capOk & rOk[q] & s8_div_window(sa[q] - vTerm) & s8_div_window(-sa[q] - vTerm);
+                  const bool fast = capOk & rOk[q] & sdiv_window(sa[q] - vTerm) & sdiv_window(-sa[q] - vTerm);
                   if (jOn[q] && !slow && !fast)
                   {
                      H = dmin(H, nH / thD[q]);
@@ -924,14 +810,13 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
             status |= failed ? (unsigned)BATOTP_ST_BISECT_FAIL : 0u;
             nfail += failed ? 1 : 0;
             stageFailed = failed;
-#if S8_FF
             // ---- CERTIFIED FAST-FORWARD of the bisection (s8_certify above) -------------------------------------------------------
             // The first check of the stage was violated and the loop goes on.  Forward sweep: the 8 paths of a wavefront run in
             // lockstep and 0.6 % of the stages bisect -- a dozen passes in which seven paths wait for one: the certificate runs
             // right here.  Reverse sweep: 22 % of the stages bisect and the passes are shared by several paths; run per arriving
             // path the block costs more than the passes it removes (profiles/r03_g_*, r04_j_*: +27 %), so there the path moves to
             // the phase PH_CERT and the block at the top of the loop serves the paths that have gathered in it (round 6).
-            if (PER == 1 && accOn && (DIR == 1 || S8_FF_REV))
+            if (PER == 1 && accOn)
             {
                const bool ffWant = (((DIR == 1) ? (a.ff & 1) : (a.ff & 2)) != 0) && first && isViol && !failed;
                if (CERT) toCert = ffWant;
@@ -943,7 +828,6 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                                 nGood, nIter);
                }
             }
-#endif
          }
          wN = fin ? ((DIR == 1) ? sddotH : sddotL) : wN;
          phase = (fin || failed) ? PH_ENDED : (toCert ? PH_CERT : phase);

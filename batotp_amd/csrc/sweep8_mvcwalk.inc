@@ -2,9 +2,6 @@
 // predictor and evalsdot).  In scope: sCur, segM, the segment's two points (mS0, mD0), (mS1, mD1), mvc, nMvc, status.  The
 // walk is the reference's comparison walk from the cached segment; a move costs one 16-byte load (the point that enters).
 {
-#if S8_TAU_RCP
-   bool walkedM = false;
-#endif
    for (;;)
    {
       const bool inM = (sCur >= mS0) & (sCur <= mS1);
@@ -12,17 +9,10 @@
       status |= (!inM & !upM & !dnM) ? (unsigned)BATOTP_ST_NONFINITE : 0u;
       const bool mvUpM = upM & (segM < nMvc - 2), mvDnM = dnM & (segM > 0);
       if (!S8_ANY(mvUpM | mvDnM)) break;
-#if S8_TAU_RCP
-      walkedM = true;
-#endif
       const double2 qM = mvc[mvUpM ? segM + 2 : (mvDnM ? segM - 1 : segM)];
       const double nS0 = mvUpM ? mS1 : (mvDnM ? qM.x : mS0), nD0 = mvUpM ? mD1 : (mvDnM ? qM.y : mD0);
       const double nS1 = mvUpM ? qM.x : (mvDnM ? mS0 : mS1), nD1 = mvUpM ? qM.y : (mvDnM ? mD0 : mD1);
       mS0 = nS0; mD0 = nD0; mS1 = nS1; mD1 = nD1;
       segM += mvUpM ? 1 : (mvDnM ? -1 : 0);
    }
-#if S8_TAU_RCP
-   // the refined reciprocal of the segment's width for evalsdot's tau (renewed when any path of the wavefront moved)
-   if (walkedM) { rM = s8_rcp_refined(mS1 - mS0); mOk = s8_div_window(mS1 - mS0) & (mS1 - mS0 > 0.0); }
-#endif
 }
