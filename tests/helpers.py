@@ -320,12 +320,42 @@ def assert_bit_equal(a, b, what):
                              f"{[ (a[tuple(i)], b[tuple(i)]) for i in idx ]}")
 
 
+def random_knots(rng, n_joints, n, scale):
+    """smooth random joint paths: a few random Fourier modes per joint, plus a straight segment and a cusp now and then"""
+    s = np.linspace(0.0, 1.0, n)
+    y = np.zeros((n_joints, n))
+    for j in range(n_joints):
+        for k in range(1, 5):
+            y[j] += rng.normal() / k * np.sin(2 * np.pi * k * s * rng.uniform(0.3, 2.0) + rng.uniform(0, 6.28))
+    if rng.random() < 0.3:
+        a = rng.integers(n // 4, n // 2)
+        y[:, a:a + n // 8] = y[:, a:a + 1] + np.linspace(0, 1, n // 8)[None, :] * rng.normal(size=(n_joints, 1)) * 0.1
+    if rng.random() < 0.3:
+        y[rng.integers(0, n_joints)] += 0.3 * np.abs(s - rng.uniform(0.2, 0.8))
+    return np.ascontiguousarray(scale * y)
+
+
+def run_sweeps(ctx, prob, ys, sres, cap):
+    """knots -> precompute -> pointwise values -> both sweeps of one batch: (result rows, [(reverse curve, forward curve, pointwise values)])"""
+    b = capi.Batch(ctx, prob, [y.shape[1] for y in ys], cap)
+    for k, y in enumerate(ys):
+        b.upload_knots(k, [y], [sres[k]])
+    b.precompute(1)
+    b.pointwise_mvc()
+    b.sweep(-1)
+    b.sweep(+1)
+    res = b.results()
+    out = [(b.curve(k, -1), b.curve(k, +1), np.stack(b.mvc(k))) for k in range(len(ys))]
+    b.close()
+    return res, out
+
+
 def set_layout(ctx, layout):
     """sweep-kernel layout of a context: 0 (automatic), 1, 8, 16, 32 lanes per path, or "flatK": 8 lanes per path, 8 paths
     per wavefront and the flat stage / bisection loop with hold K in both directions (batotp_hip_set_sweep_hold; only
     problems with joint velocity / acceleration limits alone use it, the others run the nested loops whatever K is);
     "flatKcH": the same with the reverse sweep's certificate phase at hold H; "64noff": 64 without the certified fast-forward of the
-    bisection"""
+    bisection; "GxP": G lanes per path and P paths per wavefront, the loop form left as it is set"""
     if isinstance(layout, str) and layout.startswith("oldflat"):
         # the flat instantiation of the general kernel instead of k_sweep8 (batotp_hip_set_flat_form 0)
         k = int(layout[7:])
@@ -348,10 +378,12 @@ def set_layout(ctx, layout):
         ctx.set_sweep_group(int(g))
         ctx.set_paths_per_wave(64 // int(g))
         ctx.set_sweep_hold(int(k), int(k))
-    elif layout == "64x2":
-        # k_sweep1 with TWO paths per wavefront (one per half): the cable robot in serial form with every channel as pairs
-        ctx.set_sweep_group(64)
-        ctx.set_paths_per_wave(2)
+    elif isinstance(layout, str) and "x" in layout:
+        # "8x3": 8 lanes per path, 3 paths per wavefront (the other lane groups idle); "64x2": k_sweep1 with TWO paths per wavefront
+        # (one per half): the cable robot in serial form with every channel as pairs, the compact velocity / acceleration layout
+        g, p = layout.split("x")
+        ctx.set_sweep_group(int(g))
+        ctx.set_paths_per_wave(int(p))
     elif layout == "64noff":
         # one path per wavefront (k_sweep1) with every iteration of the bisection checked (batotp_hip_set_fast_forward 0)
         ctx.set_sweep_group(64)

@@ -6,41 +6,13 @@ import numpy as np
 import pytest
 
 from helpers import assert_bit_equal, set_layout
+from helpers import random_knots as _random_knots, run_sweeps as _run   # (shared with test_gpu_sweep_plan.py)
 from batotp_amd import capi, pathgen
 
 pytestmark = pytest.mark.gpu
 
 # BATOTP_FUZZ_SCALE=k runs k times as many seeds (the default keeps the GPU suite short)
 _SCALE = max(1, int(os.environ.get("BATOTP_FUZZ_SCALE", "1")))
-
-
-def _random_knots(rng, n_joints, n, scale):
-    """smooth random joint paths: a few random Fourier modes per joint, plus a straight segment and a cusp now and then"""
-    s = np.linspace(0.0, 1.0, n)
-    y = np.zeros((n_joints, n))
-    for j in range(n_joints):
-        for k in range(1, 5):
-            y[j] += rng.normal() / k * np.sin(2 * np.pi * k * s * rng.uniform(0.3, 2.0) + rng.uniform(0, 6.28))
-    if rng.random() < 0.3:
-        a = rng.integers(n // 4, n // 2)
-        y[:, a:a + n // 8] = y[:, a:a + 1] + np.linspace(0, 1, n // 8)[None, :] * rng.normal(size=(n_joints, 1)) * 0.1
-    if rng.random() < 0.3:
-        y[rng.integers(0, n_joints)] += 0.3 * np.abs(s - rng.uniform(0.2, 0.8))
-    return np.ascontiguousarray(scale * y)
-
-
-def _run(ctx, prob, ys, sres, cap):
-    b = capi.Batch(ctx, prob, [y.shape[1] for y in ys], cap)
-    for k, y in enumerate(ys):
-        b.upload_knots(k, [y], [sres[k]])
-    b.precompute(1)
-    b.pointwise_mvc()
-    b.sweep(-1)
-    b.sweep(+1)
-    res = b.results()
-    out = [(b.curve(k, -1), b.curve(k, +1), np.stack(b.mvc(k))) for k in range(len(ys))]
-    b.close()
-    return res, out
 
 
 @pytest.mark.parametrize("seed", range(6 * _SCALE))
