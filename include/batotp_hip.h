@@ -295,7 +295,11 @@ int  batotp_hip_download_mvc(batotp_batch *batch, int32_t path, double *sdot_max
 /* The integrated curves of paths [path0, path0 + n_paths) -- which = -1 reverse, +1 forward -- packed path after path
  * into dst_dev (DEVICE memory with room for dst_points (s, sdot) pairs of doubles); *total_points = pairs written.  This
  * is the send buffer of the multi-GPU curve gather (traj.sMVC / traj.sdot after sweep, reference ba.cpp:1154-1190): the
- * curves have different lengths, so a size exchange + grouped send/recv moves them (batotp_amd/dist.py). */
+ * curves have different lengths, so a size exchange + grouped send/recv moves them (batotp_amd/dist.py).
+ * Errors: a range outside the batch, a negative count, which == 0 or total_points == NULL give BATOTP_ERR_ARG and touch
+ * nothing; a curve that is gone (BATOTP_F_CURVES_IN_PLACE after the forward sweep, BATOTP_F_MVC_IN_CURVES after a pointwise
+ * evaluation) gives BATOTP_ERR_STATE with *total_points = 0; dst_dev == NULL or dst_points too small for a total > 0 gives
+ * BATOTP_ERR_ARG with *total_points = the room needed, and nothing is written.  Before any sweep the total is 0 (BATOTP_OK). */
 int  batotp_hip_pack_curves(batotp_batch *batch, int32_t which, int32_t path0, int32_t n_paths, void *dst_dev,
                             int64_t dst_points, int64_t *total_points);
 /* device pointer + element count of the per-path result table (batotp_path_result[n_paths]) */

@@ -88,6 +88,22 @@ class Case:
         return int(max(self.expected["n_rev"], self.expected["n_fwd"]) + 64)
 
 
+class PrefixCase:
+    """the first n knots of a golden case as a path of its own, under the problem description `problem` (one per batch)"""
+
+    def __init__(self, case, n, problem):
+        self.name, self.problem, self.sres = f"{case.name}[:{n}]", problem, case.sres
+        self.y = np.ascontiguousarray(case.y[:, :n])
+        self._max_steps = case.max_steps()
+
+    @property
+    def n(self):
+        return self.y.shape[1]
+
+    def max_steps(self):
+        return self._max_steps     # (a prefix needs no more steps than the whole path)
+
+
 class ResampleCase:
     """taught points + resampling parameters of a golden case; expected output = its knots.npz"""
 

@@ -18,24 +18,30 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, names, q):
+def _worker(rank, world, port, names, q, backend="gloo", load_library=helpers.load_oracle, device=None):
+    """one rank: its share of the paths through the library `load_library` returns, rows and both curves gathered over `backend`;
+    device: None (host tensors, the oracle's "device" memory is host memory) or "cuda" (RCCL: rank r owns cuda:r)"""
     sys.path.insert(0, helpers.ROOT)
     sys.path.insert(0, os.path.join(helpers.ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    import torch
     import torch.distributed as dist
     from batotp_amd import capi
     from batotp_amd import dist as bdist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dev = torch.device(device, rank) if device is not None else None
+    if dev is not None:
+        torch.cuda.set_device(dev)
+    dist.init_process_group(backend, rank=rank, world_size=world, **({"device_id": dev} if dev is not None else {}))
     try:
         lo, hi = bdist.shard_range(len(names), rank, world)
         cases = [helpers.Case(n) for n in names[lo:hi]]
         for c in cases:
             c.problem = helpers.Case(names[0]).problem
-        ctx = capi.Context(helpers.load_oracle(), 0)
+        ctx = capi.Context(load_library(), rank if dev is not None else 0)
         outs = helpers.run_pipeline(ctx, cases, mvc=False, details=False) if cases else []
         local = np.array([o["result"] for o in outs], dtype=capi.RESULT_DTYPE) if outs else np.zeros(0, dtype=capi.RESULT_DTYPE)
-        allres = bdist.gather_results(local)
+        allres = bdist.gather_results(local, dev)
         # the variable-length part: both curves of every path, to rank 0
         b = None                 # (a rank without a share has no batch: it takes part in the collectives and sends nothing)
         if cases:
@@ -43,7 +49,7 @@ def _worker(rank, world, port, names, q):
             for k, c in enumerate(cases):
                 b.upload_knots(k, [c.y], [c.sres])
             b.optimize()
-        curves = {w: bdist.gather_curves(b, w) for w in (-1, 1)}
+        curves = {w: bdist.gather_curves(b, w, device=dev) for w in (-1, 1)}
         if rank == 0:
             q.put((allres.tobytes(), {w: [(s.tobytes(), sd.tobytes()) for s, sd in curves[w]] for w in curves}))
     finally:

@@ -354,6 +354,60 @@ def test_single_path_with_seven_paths_per_wavefront(hip_lib, oracle_ctx, family)
 
 
 # ---------------------------------------------------------------------------------------------
+# the software prefetch of the general kernel (batotp_hip_set_sweep_prefetch): "never changes a result"
+# ---------------------------------------------------------------------------------------------
+# SweepArgs::touch is read by k_sweep alone -- its nested loops (bit 0: touch_ahead, bit 1, forward sweep: touch_curve_ahead) and its
+# own flat instantiation (bit 0) -- and by neither k_sweep8 nor k_sweep1, so every configuration forces a shape that k_sweep runs.
+# Both touches clamp their address into the path's own arrays: [row 0, row n - 1] of the spline rows or pairs, and [point 0, point
+# nMvc - 1] of the reverse curve; the forward sweep of k_sweep returns before its first touch when the reverse curve has fewer than two
+# points, so nMvc - 1 >= 1 wherever touch_curve_ahead runs.
+PREFETCH = [(0, 0), (1, 1), (0, 2), (1, 3), (-1, -1)]
+PREFETCH_SHAPES = {
+    # name: (layout of helpers.set_layout, problem flags, launch on record)
+    "rows_32x1": ("32", 0, (32, 1, -1)),            # one path per wavefront: the automatic setting touches rows and curve
+    "rows_16x3": ("16x3", 0, (16, 3, -1)),          # several paths per wavefront: the automatic setting never sets the forward bits
+    "compact_32x1": ("32", COMPACT, (32, 1, -1)),   # the pair stream (FEAT < 0)
+    "rows_flat_8x8": ("oldflat4", 0, (8, 8, 4)),    # k_sweep's own flat loop instead of k_sweep8
+}
+_prefetch_ref = []
+
+
+def _prefetch_batch(oracle_ctx):
+    """five paths of 4 knots (a reverse curve of 23 points, the shortest here) .. the full golden length, and the oracle's run of them"""
+    if not _prefetch_ref:
+        g, s = helpers.Case("GEN7DOF"), helpers.Case("synth_gen7dof_s0")
+        cuts = [helpers.PrefixCase(c, n, g.problem) for c, n in ((g, 4), (s, 37), (g, g.n), (s, 300), (g, 120))]
+        _prefetch_ref.append((cuts, helpers.run_pipeline(oracle_ctx, cuts, mvc=False, details=False)))
+    return _prefetch_ref[0]
+
+
+@pytest.mark.parametrize("touch", PREFETCH, ids=lambda t: f"touch{t[0]}_{t[1]}")
+@pytest.mark.parametrize("shape", list(PREFETCH_SHAPES))
+def test_prefetch_switch_never_changes_a_result(hip_lib, oracle_ctx, shape, touch):
+    cuts, ref = _prefetch_batch(oracle_ctx)
+    layout, flags, launch = PREFETCH_SHAPES[shape]
+    ctx = capi.Context(hip_lib, 0)
+    set_layout(ctx, layout)
+    ctx.set_sweep_prefetch(*touch)
+    prob = capi.Problem.from_buffer_copy(bytes(cuts[0].problem))
+    prob.flags |= flags
+    b = capi.Batch(ctx, prob, [c.n for c in cuts], max(c.max_steps() for c in cuts))
+    for k, c in enumerate(cuts):
+        b.upload_knots(k, [c.y], [c.sres])
+    b.optimize()
+    rows = b.results()
+    assert b.last_sweep_launch(-1) == launch and b.last_sweep_launch(+1) == launch, (b.last_sweep_launch(-1), b.last_sweep_launch(+1))
+    for k, o in enumerate(ref):
+        what = f"{shape} prefetch {touch} path {k}"
+        for f in rows.dtype.names:
+            assert rows[k][f] == o["result"][f], (what, f, rows[k][f], o["result"][f])
+        for which, key in ((-1, "rev"), (+1, "fwd")):
+            s, sd = b.curve(k, which)
+            assert_bit_equal(s, o[key][0], f"{what} {key} s"); assert_bit_equal(sd, o[key][1], f"{what} {key} sdot")
+    b.close(); ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------
 # part B: the automatic plan at its switching sizes.  (lanes per path, paths per wavefront, hold) of the reverse and of the forward
 # sweep; H4 / H8: hold 4 / 8 of the flat loop where its gate is open (flat_loop_status() == 1), the nested loops (-1) otherwise
 # ---------------------------------------------------------------------------------------------
