@@ -333,7 +333,8 @@ class Context:
         self.library.check(self.library.lib.batotp_hip_set_sweep_hold(self.handle, reverse, forward), "set_sweep_hold")
 
     def set_flat_form(self, form: int):
-        """1 = k_sweep8 (default), 0 = the flat instantiation of the general kernel (include/batotp_hip.h)"""
+        """1 = k_sweep8, in the forward sweep at hold 8 its lockstep form k_sweep8_lock (default); 2 = k_sweep8's flat loop in the
+        forward sweep too (the previous form: A/B, parity); 0 = the flat instantiation of the general kernel (include/batotp_hip.h)"""
         self.library.check(self.library.lib.batotp_hip_set_flat_form(self.handle, form), "set_flat_form")
 
     def set_sweep_prefetch(self, reverse: int, forward: int):

@@ -19,6 +19,7 @@
 #include "kernels.hip.h"
 #include "sweep1.hip.h"
 #include "sweep8.hip.h"
+#include "sweep8_fwd.hip.h"
 #include "pointwise_va.hip.h"
 #include "spline_stream.hip.h"
 #include "spline_tile.hip.h"
@@ -118,7 +119,9 @@ struct batotp_ctx
    // toolchain the loop was validated with and the canary of flatLoopStatus agreed with the nested loops on this device),
    // -1 = built by another toolchain, -2 = the canary disagreed, -3 = the canary could not run
    int splineTiles = -1;  // K1 in tiles of knots (spline_tile.hip.h): -1 automatic (small batches), 1 always, 0 never
-   int flatForm = 1;      // flat loop of the 8-lane layout: 1 = k_sweep8 (sweep8.hip.h), 0 = k_sweep's own flat instantiation (A/B, parity)
+   int flatForm = 1;      // flat loop of the 8-lane layout: 1 = k_sweep8 (sweep8.hip.h) and, forward at hold 8, its lockstep form k_sweep8_lock
+                          // (sweep8_fwd.hip.h); 2 = k_sweep8's flat loop in the forward sweep too (the previous form: A/B, parity);
+                          // 0 = k_sweep's own flat instantiation (A/B, parity)
    int fastForward = 1;   // certified fast-forward of the bisection in the sweep kernels that have it (bisect_fast_forward)
    int certHold = -1;     // k_sweep8, reverse sweep: hold of the certificate phase (-1 automatic, 0 = no certificate there, 1..8)
    int poison = 0;        // debug aid (batotp_hip_set_poison): every workspace / batch allocation is filled with 0xFF bytes before use
@@ -143,6 +146,7 @@ struct SweepPlan
    int hold = -1, touch = 0, ff = 0, holdc = 0; // as in SweepArgs
    bool flat = false;   // k_sweep / k_sweep8: the flat stage / bisection loop
    bool form8 = false;  // ... as k_sweep8 (sweep8.hip.h)
+   bool lock = false;   // ... forward, 8 lanes, hold 8: as k_sweep8_lock (sweep8_fwd.hip.h)
    int ff1 = 0;         // k_sweep1, torque limits: form of the certified fast-forward (template parameter FF)
 };
 
@@ -424,7 +428,7 @@ extern "C" int batotp_hip_set_sweep_hold(batotp_ctx *ctx, int32_t reverse, int32
 
 extern "C" int batotp_hip_set_flat_form(batotp_ctx *ctx, int32_t form)
 {
-   if (!ctx || form < 0 || form > 1) return BATOTP_ERR_ARG;
+   if (!ctx || form < 0 || form > 2) return BATOTP_ERR_ARG;
    ctx->flatForm = form;
    return BATOTP_OK;
 }
@@ -1409,7 +1413,8 @@ static int flatCanaryOnce(batotp_ctx *ctx, bool compact, bool *same)
    std::vector<double2> curves[2], curvesF[2];
    const int holdSaved[2] = {ctx->sweepHold[0], ctx->sweepHold[1]}, groupSaved = ctx->sweepGroup, ppwSaved = ctx->pathsPerWave;
    const int formSaved = ctx->flatForm, ffSaved = ctx->fastForward, certSaved = ctx->certHold;
-   // the canary compares exactly what the automatic choice launches: 8 lanes per path, k_sweep8, the certified fast-forward on --
+   // the canary compares exactly what the automatic choice launches: 8 lanes per path, k_sweep8 in the reverse sweep and its lockstep
+   // form k_sweep8_lock in the forward sweep (flat form 1), the certified fast-forward on --
    // whatever the developer switches of this context say at the moment
    ctx->sweepGroup = 8; ctx->pathsPerWave = 8; ctx->flatForm = 1; ctx->fastForward = 1; ctx->certHold = -1;
    rc = batotp_hip_upload_knots(b, 0, B, y.data(), sres.data());
@@ -1583,17 +1588,22 @@ static SweepPlan planSweep(const batotp_batch *b, int dir)
    int hold = ctx->sweepHold[k];
    // automatic: the flat stage / bisection loop for the reverse sweep (measured on the bench batches: -25 % with hold 4,
    // bit-identical results) -- where it exists (below) and only behind the gate of flatLoopStatus: validated toolchain and
-   // a canary on this device --, the nested loops for the forward sweep (which does not gain)
+   // a canary on this device --, and hold 8 for the forward sweep, which then runs in lockstep (k_sweep8_lock, sweep8_fwd.hip.h)
    if (hold == -2)
    {
-      // reverse: hold 4 (round 2: 855 against 1130 ms on the UR6 bench batch).  Forward: k_sweep8 with hold 8 -- the nested
-      // loops' schedule, every path of the wavefront starts its stage together -- because that kernel executes 9 % fewer
-      // vector and 37 % fewer scalar instructions than the nested form of k_sweep (round 4: 444 against 560 ms at 16 384
-      // paths, profiles/r04_a_*); the general kernel's own flat form does not gain in the forward sweep and keeps the nested loops
-      // Only the form the canary of flatLoopStatus compares: 8 lanes per path in k_sweep8.  With 2 or 4 lanes per path, or with
-      // k_sweep's own flat instantiation selected (batotp_hip_set_flat_form 0), the automatic choice keeps the nested loops --
+      // reverse: hold 4 (round 2: 855 against 1130 ms on the UR6 bench batch).  Forward: hold 8 -- the nested loops' schedule,
+      // every path of the wavefront starts its stage together.  k_sweep8 at hold 8 executes 9 % fewer vector and 37 % fewer
+      // scalar instructions than the nested form of k_sweep (round 4: 444 against 560 ms at 16 384 paths, profiles/r04_a_*), and
+      // the plan below launches its lockstep form k_sweep8_lock there (1654 against 1958 ms at the headline, profiles/fwd_lockstep_*;
+      // batotp_hip_set_flat_form 2 keeps k_sweep8 itself); the general kernel's own flat form does not gain in the forward sweep and
+      // keeps the nested loops.
+      // Only the form the canary of flatLoopStatus compares: 8 lanes per path in k_sweep8 / k_sweep8_lock (the canary runs flat form 1,
+      // so the forward kernel it validates is the lockstep one; flat form 2 goes through the same gate and has no canary of its own:
+      // it is the developer's A/B switch, checked against the lockstep kernel and the oracle by tests/test_gpu_sweep8_lockstep.py).
+      // With 2 or 4 lanes per path, or with k_sweep's own flat instantiation selected (batotp_hip_set_flat_form 0), the automatic
+      // choice keeps the nested loops --
       // an explicit batotp_hip_set_sweep_hold remains the developer's switch for those.
-      const bool candidate = lanes == 8 && p.feat <= 0 && p.uni && ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
+      const bool candidate = lanes == 8 && p.feat <= 0 && p.uni && ctx->flatForm != 0 && b->cap < ((int64_t)1 << 30);
       hold = -1;
       if (candidate && flatLoopStatus(b->ctx) == 1) hold = dir == -1 ? 4 : 8;
    }
@@ -1605,7 +1615,9 @@ static SweepPlan planSweep(const batotp_batch *b, int dir)
    // Cartesian limits always run the nested loops, and so do paths with uploaded (non-uniform) sites.
    p.flat = (lanes == 8 || lanes == 4 || lanes == 2) && hold >= 0 && p.feat <= 0 && p.uni;
    // the flat loop of the 8-lane layout written for the instruction count (sweep8.hip.h); 32-bit step counters
-   p.form8 = p.flat && (lanes == 8 || lanes == 4) && ctx->flatForm == 1 && b->cap < ((int64_t)1 << 30);
+   p.form8 = p.flat && (lanes == 8 || lanes == 4) && ctx->flatForm != 0 && b->cap < ((int64_t)1 << 30);
+   // forward at hold 8 nothing drifts apart: the lockstep form with a scalar stage index (sweep8_fwd.hip.h; profiles/fwd_lockstep_*)
+   p.lock = p.form8 && lanes == 8 && dir == 1 && hold == 8 && ctx->flatForm == 1;
    return p;
 }
 
@@ -1619,7 +1631,8 @@ static void launchSweep(hipStream_t st, const SweepPlan &p, const SweepArgs &a)
       if (p.form8 && F <= 0)
       {
          constexpr int F8 = F <= 0 ? F : 0, G8 = G == 4 ? 4 : 8;
-         if (a.dir == 1) hipLaunchKernelGGL((k_sweep8<G8, F8, 1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
+         if (p.lock) hipLaunchKernelGGL((k_sweep8_lock<F8>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
+         else if (a.dir == 1) hipLaunchKernelGGL((k_sweep8<G8, F8, 1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
          else hipLaunchKernelGGL((k_sweep8<G8, F8, -1>), dim3(grid), dim3(S8_BLOCK), 0, st, a);
       }
       else if (p.flat) hipLaunchKernelGGL((k_sweep<G, F, true, ((G == 8 || G == 4 || G == 2) && F <= 0)>), dim3(grid), dim3(K4_BLOCK), 0, st, a);

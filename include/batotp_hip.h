@@ -330,8 +330,10 @@ int  batotp_hip_set_paths_per_wave(batotp_ctx *ctx, int32_t n);
 int  batotp_hip_set_sweep_hold(batotp_ctx *ctx, int32_t reverse, int32_t forward);
 /* which code runs that flat loop in the 8-lane layout: 1 (default) = k_sweep8 (batotp_amd/csrc/sweep8.hip.h: the same loop and
  * arithmetic -- reference batotp/ba.cpp:1053-1123 with sdotLim :1204-1236 and the bisection :1248-1332 -- hand-structured for
- * the instruction count: one level of divergence, wavefront-uniform segment walks, curve points stored 64 bytes at a time),
- * 0 = the flat instantiation of the general kernel k_sweep (kept for A/B runs and as a second implementation the parity tests
+ * the instruction count: one level of divergence, wavefront-uniform segment walks, curve points stored 64 bytes at a time)
+ * and, for the forward sweep of 8 lanes per path at hold 8, its lockstep form k_sweep8_lock (batotp_amd/csrc/sweep8_fwd.hip.h:
+ * the stage index is a scalar, the stage values stay in registers), 2 = k_sweep8's flat loop in the forward sweep too (the
+ * previous form, kept for A/B runs and parity), 0 = the flat instantiation of the general kernel k_sweep (kept for A/B runs and as a second implementation the parity tests
  * compare).  Never changes a result. */
 int  batotp_hip_set_flat_form(batotp_ctx *ctx, int32_t form);
 /* The gate of that automatic choice.  The flat loop's torque instantiation gave wrong results with the toolchain named

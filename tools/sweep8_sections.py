@@ -6,7 +6,8 @@
     python tools/sweep8_sections.py --lib /tmp/libs8prof.so --paths 16384
 
 The headline batch of bench.py (GEN7DOF, N ~ 1e5, curves in place, pointwise values in the curve slots); per wavefront the
-kernel leaves 16 counters (sweep8.hip.h, S8_PROFILE)."""
+kernel leaves 16 counters (sweep8.hip.h, S8_PROFILE).  The forward sweep at hold 8 runs k_sweep8_lock (sweep8_fwd.hip.h), which keeps the
+same counters (a pass there is a constraint check of the wavefront); --flat-form 2 runs k_sweep8's flat loop in the forward sweep too."""
 import argparse
 import ctypes as C
 import os
@@ -25,6 +26,7 @@ ap.add_argument("--knots", type=int, default=100000)
 ap.add_argument("--distinct", type=int, default=256)
 ap.add_argument("--hold", type=int, nargs=2, default=None)
 ap.add_argument("--cert-hold", type=int, default=None, help="batotp_hip_set_cert_hold (reverse sweep: the certificate phase)")
+ap.add_argument("--flat-form", type=int, default=None, help="batotp_hip_set_flat_form (2: k_sweep8's flat loop in the forward sweep too)")
 a = ap.parse_args()
 
 lib = capi.Library(a.lib)
@@ -33,6 +35,8 @@ if a.hold:
     hip.set_sweep_hold(*a.hold)
 if a.cert_hold is not None:
     hip.set_cert_hold(a.cert_hold)
+if a.flat_form is not None:
+    hip.set_flat_form(a.flat_form)
 if a.paths > a.distinct:
     hip.set_path_order(0)   # tiled copies of a path must not become neighbours in a wavefront (they would run in lockstep)
 inp = bench.Inputs(hip, a.workload, a.knots, [1000 + k for k in range(a.distinct)])
