@@ -35,6 +35,8 @@ ST_NONFINITE, ST_SHORT, ST_SEG_ERROR = 1 << 3, 1 << 4, 1 << 5
 # path kinds / status bits of the resampler
 PATH_JOINT, PATH_CART, PATH_BOTH = 1, 2, 3
 RS_TOO_SHORT, RS_IDENTICAL, RS_CAPACITY, RS_SMALL_STEP, RS_SEG_ERROR = 1, 2, 4, 8, 16
+# OutputParams.integ_res: every path of the range is sampled with its own step (BATOTP_OUT_STEP_PER_PATH)
+OUT_STEP_PER_PATH = 0.0
 
 _d8 = C.c_double * 8
 
@@ -469,8 +471,12 @@ class Resampled:
 class Output:
     """Constant-time output trajectories of a range of paths of a batch (batotp_hip_output), resident on the device."""
 
-    def __init__(self, batch: "Batch", prm: OutputParams, path0: int, n_paths: int):
+    def __init__(self, batch: "Batch", prm: OutputParams, path0: int, n_paths: int, per_path_steps: bool = False):
+        """per_path_steps: every path is sampled with its own integration step (Batch.set_path_integ_res) instead of prm.integ_res"""
         self.lib, self.L = batch.lib, batch.L
+        if per_path_steps:
+            prm = OutputParams.from_buffer_copy(bytes(prm))
+            prm.integ_res = OUT_STEP_PER_PATH
         self.n_paths, self.n_joints = n_paths, prm.n_joints
         self.handle = C.c_void_p()
         self.L.check(self.lib.batotp_hip_output(batch.handle, C.byref(prm), path0, n_paths, C.byref(self.handle)), "batotp_hip_output")

@@ -16,29 +16,27 @@ struct OutPath
 {
    int64_t off1;    // first point of this path in the stage-1 arrays (sOut, seg, th1)
    int64_t off2;    // ... in the down-sampled arrays (th2, sol2)
-   int64_t offF;    // ... in the final array
+   int64_t offF;    // ... in the final-stage arrays of the launch (dense over the paths of the launch)
+   int64_t offD;    // ... in the result of the chunk, which stays in path order (= offF unless the chunk is staged)
    int64_t offS;    // first element of this path's s(t) second derivatives
    int32_t p;       // path of the batch
    int32_t nFwd;    // points of the forward curve
    int32_t n1;      // nOut of ba.cpp:1683
    int32_t n2;      // points after smoothing + down-sampling (= n1 without smoothing)
    int32_t nF;      // final points
-   int32_t pad;
+   int32_t window;  // (int)smoothing factor of this path when it is smoothed, else 0
    double tStep;    // time step of the forward curve (tMVC[i] = tStep*i)
+   double vfactT, afactT; // 1/tfact and its square, tfact = (output resolution)/(smoothing factor) of this path (ba.cpp:1754)
 };
 
 struct OutParams
 {
    int nJ;          // joint rows
    int R;           // rows per output point: joints (+ 3 Cartesian + 3 torque rows for the cable robot)
-   int window;      // (int)_outSmoothFact when smoothing, else 0
-   int reinterp;
    int compact;     // the batch keeps (value, second derivative) pairs instead of coefficient rows
    int kmC;         // ... channels per knot in the pair array (Cin, or C when all channels are pairs)
    int svd;         // BATOTP_F_SVD: the cable tensions through the Jacobi SVD instead of the LU
    int C, Cin;
-   double outRes;
-   double vfactT, afactT; // cable robot: 1/tfact and its square, tfact = outRes/smoothFact (ba.cpp:1754)
    double pmat[9];
 };
 
@@ -237,7 +235,7 @@ __global__ void k_out_trq(OutParams P, const OutPath *__restrict__ paths, int K,
       const int64_t at = op.off1 * P.R + (int64_t)r * n1 + seg;
       const Coef4 k = coeffs_from_sol(sol1[at], sol1[at + 1], src[at], src[at + 1]);
       val[r] = k.c3 * tau3 + k.c2 * tau2 + k.c1 * tau + k.c0;
-      if (r >= 3) d2c[r - 3] = (6 * k.c3 * tau + 2 * k.c2) * P.afactT;
+      if (r >= 3) d2c[r - 3] = (6 * k.c3 * tau + 2 * k.c2) * op.afactT;
    }
    double b[3], A[9], xs[3];
 #pragma unroll
@@ -353,8 +351,8 @@ __global__ void k_out_serial_eval(OutParams P, const OutPath *__restrict__ paths
       const int64_t at = op.off1 * P.R + (int64_t)j * n1 + seg;
       const Coef4 k = coeffs_from_sol(solC[at], solC[at + 1], src[at], src[at + 1]);
       const double v = k.c3 * tau3 + k.c2 * tau2 + k.c1 * tau + k.c0;          // spline.cpp:149-151
-      const double v1 = (3 * k.c3 * tau2 + 2 * k.c2 * tau + k.c1) * P.vfactT;
-      const double v2 = (6 * k.c3 * tau + 2 * k.c2) * P.afactT;
+      const double v1 = (3 * k.c3 * tau2 + 2 * k.c2 * tau + k.c1) * op.vfactT;
+      const double v2 = (6 * k.c3 * tau + 2 * k.c2) * op.afactT;
       double *__restrict__ sp = sampT + op.off1 * P.Cin * 3 + (int64_t)j * 3 * n1;
       sp[i] = v; sp[n1 + i] = v1; sp[2 * (int64_t)n1 + i] = v2;
       pack[op.off1 * P.nJ + (int64_t)j * n1 + i] = v;
@@ -383,7 +381,7 @@ __global__ void k_out_trq_sum(OutParams P, const OutPath *__restrict__ paths, in
 // Pose rows of a BOTH path at the very end of the stage: BA::q2aaVect (ba.cpp:384-403) with q2aa (util.cpp:562-581).  The
 // working arrays carry position + quaternion (7 Cartesian rows), the result position + axis-angle (6).
 //   k_out_q_norm  the vector part's norm and q0 of every final point, packed [2][nF] per path at offF*2 (host atan2 table)
-//   k_out_q2aa    src [Rw][nF] -> dst [Rw - 1][nF]; at = atan2(norm, q0) per point from the host, or nullptr (device libm)
+//   k_out_q2aa    src [Rw][nF] at offF -> dst [Rw - 1][nF] at offD (the path's place in the result); at = atan2(norm, q0) per point from the host, or nullptr (device libm)
 // ---------------------------------------------------------------------------------------------
 __global__ void k_out_q_norm(int nJ, int Rw, const OutPath *__restrict__ paths, int K, const double *__restrict__ src, double *__restrict__ pack,
                              int64_t total)
@@ -408,7 +406,7 @@ __global__ void k_out_q2aa(int nJ, int Rw, const OutPath *__restrict__ paths, in
    const int i = (int)(g - op.offF), n = op.nF;
    if (i >= n) return;
    const double *__restrict__ s = src + op.offF * Rw + i;
-   double *__restrict__ o = dst + op.offF * (Rw - 1) + i;
+   double *__restrict__ o = dst + op.offD * (Rw - 1) + i;
    for (int r = 0; r < nJ + 3; ++r) o[(int64_t)r * n] = s[(int64_t)r * n];
    const double q0 = s[(int64_t)(nJ + 3) * n], q1 = s[(int64_t)(nJ + 4) * n], q2 = s[(int64_t)(nJ + 5) * n], q3 = s[(int64_t)(nJ + 6) * n];
    const double norme = sqrt(q1 * q1 + q2 * q2 + q3 * q3);
@@ -433,7 +431,7 @@ __global__ void k_out_down(OutParams P, const OutPath *__restrict__ paths, int K
    const OutPath op = paths[out_find_path(paths, K, g, 2)];
    const int i = (int)(g - op.off2), nIn = op.n1, nDown = op.n2;
    if (i >= nDown) return;
-   int w = P.window < nIn ? P.window : nIn;
+   int w = op.window < nIn ? op.window : nIn;
    const int half = w / 2 + w % 2 - 1;
    w = 2 * half + 1;
    const double site = ((double)(nIn - 1) / (double)(nDown - 1)) * (double)i;
@@ -470,6 +468,19 @@ __global__ void k_out_user(OutParams P, const OutPath *__restrict__ paths, int K
       const Coef4 k = coeffs_from_sol(sol2[at], sol2[at + 1], th2[at], th2[at + 1]);
       thF[op.offF * P.R + (int64_t)c * nUser + i] = k.c3 * tau3 + k.c2 * tau2 + k.c1 * tau + k.c0;
    }
+}
+
+// A chunk whose paths do not all take the same route (some smoothed or re-interpolated, others not) runs one launch sequence
+// per route into a staging array that is dense over the paths of that route; this moves the rows [R][nF] of every such path
+// to its place in the result, which stays in path order.  A plain copy: one lane per final point.
+__global__ void k_out_place(int R, const OutPath *__restrict__ paths, int K, const double *__restrict__ src, double *__restrict__ dst, int64_t total)
+{
+   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   if (g >= total) return;
+   const OutPath op = paths[out_find_path(paths, K, g, 3)];
+   const int i = (int)(g - op.offF), n = op.nF;
+   if (i >= n) return;
+   for (int c = 0; c < R; ++c) dst[op.offD * R + (int64_t)c * n + i] = src[op.offF * R + (int64_t)c * n + i];
 }
 
 } // namespace bk

@@ -179,6 +179,9 @@ public:
    // milliseconds the last optimizeBatch() spent in the output stage: wall clock incl. downloads, and device kernels
    double getLastOutputMs() const { return _lastOutputMs; }
    double getLastOutputKernelMs() const { return _lastOutputKernelMs; }
+   // batotp_hip_output calls that produced the trajectories of the last optimizeBatch(): one per range of up to 1024 paths
+   // where the library samples every path with its own integration step, else one per run of equal step (all devices together)
+   int getLastOutputCalls() const { return _lastOutputCalls; }
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
    // traj.sres and the knot count in traj.nPts.  No device call.
@@ -345,6 +348,7 @@ private:
    double _lastResampleMs = 0;
    bool _deviceOutput = true;
    double _lastOutputMs = 0, _lastOutputKernelMs = 0;
+   int _lastOutputCalls = 0;
    int _deviceId = 0;
    std::vector<int> _devices;              // optimizeBatch over several GPUs (empty: _deviceId only)
    int optimizeBatchOnDevice(std::vector<Traj> &trajs);

@@ -799,6 +799,7 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
    bool broken = false;
    setErrorOptimization(NO_ERROR);
    _lastResampleMs = _lastOutputMs = _lastOutputKernelMs = 0;
+   _lastOutputCalls = 0;
    for (size_t d = 0; d < nDev; ++d)
    {
       std::move(part[d].begin(), part[d].end(), trajs.begin() + lo[d]);
@@ -807,6 +808,7 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
       _lastResampleMs = std::max(_lastResampleMs, worker[d]._lastResampleMs);
       _lastOutputMs = std::max(_lastOutputMs, worker[d]._lastOutputMs);
       _lastOutputKernelMs = std::max(_lastOutputKernelMs, worker[d]._lastOutputKernelMs);
+      _lastOutputCalls += worker[d]._lastOutputCalls;
    }
    // what a single-device run leaves in the object (run state a later writeOutputData / interpOutputData reads)
    _isInterpolated = worker[0]._isInterpolated;
@@ -1188,31 +1190,42 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
    batotp_hip_resampled_destroy(rs.r);
    rs.r = nullptr;
 
-   // 3) output stage behind the C-ABI (batotp_hip_output): only the finished trajectories come back, in ranges of paths
-   //    that integrate with the same step (one step for the whole batch unless the automatic integration resolution is
-   //    on) and of at most 1024 paths, so that their device copy stays small
+   // 3) output stage behind the C-ABI (batotp_hip_output): only the finished trajectories come back, in ranges of at most
+   //    1024 paths, so that their device copy stays small.  A range whose paths integrate with one step (every range unless
+   //    the automatic integration resolution is on) names that step; one whose steps differ asks for every path's own
+   //    (BATOTP_OUT_STEP_PER_PATH).  A library that serves one step per call refuses that value with BATOTP_ERR_ARG: from
+   //    then on the ranges are the runs of equal step, one call each, as they were before the value existed.
    const std::chrono::steady_clock::time_point tOut0 = std::chrono::steady_clock::now();
    double kernelMs = 0;
    const size_t range = 1024;
    std::vector<double> flatAll;
    std::vector<int64_t> nPtsOut;
    std::vector<double> sresOut;
+   bool perPathServed = true;
+   int outputCalls = 0;
    for (size_t k0 = 0; k0 < live.size();)
    {
-      size_t cnt = 1;
-      while (k0 + cnt < live.size() && cnt < range && integOf[k0 + cnt] == integOf[k0]) ++cnt;
-      const double h = integOf[k0];
-      if (!(h > 0))
+      size_t cnt = std::min(range, live.size() - k0), same = 1;
+      while (same < cnt && integOf[k0 + same] == integOf[k0]) ++same;
+      const bool perPath = same < cnt && perPathServed;
+      if (!perPath) cnt = same;
+      if (!perPath && !(integOf[k0] > 0))
       {
          // no integration step, no trajectory (the rule gave NaN: a robot without Cartesian limits)
          for (size_t q = 0; q < cnt; ++q) ok[live[k0 + q]] = 0;
          k0 += cnt;
          continue;
       }
-      outPrm.integ_res = h;
+      outPrm.integ_res = perPath ? BATOTP_OUT_STEP_PER_PATH : integOf[k0];
       OutputGuard og;
       rc = batotp_hip_output(g.b, &outPrm, (int32_t)k0, (int32_t)cnt, &og.o);
+      if (perPath && rc == BATOTP_ERR_ARG)
+      {
+         perPathServed = false; // the same paths again, as runs of equal step
+         continue;
+      }
       if (rc) return fail("output", rc);
+      ++outputCalls;
       nPtsOut.assign(cnt, 0);
       sresOut.assign(cnt, 0.0);
       rc = batotp_hip_output_info(og.o, nPtsOut.data(), sresOut.data());
@@ -1235,6 +1248,8 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          const size_t k = k0 + q;
          Traj &t = trajs[live[k]];
          const batotp_path_result &r = res[k];
+         const double h = integOf[k];
+         if (!(h > 0)) { ok[live[k]] = 0; continue; } // (no step, no trajectory: such a path has no points in the range either)
          if ((r.status_rev | r.status_fwd) & BATOTP_ST_MAX_INTEG_TIME) setErrorOptimization(MAX_INTEGRATION_TIME);
          const int64_t n = nPtsOut[q];
          if (n == 0) { ok[live[k]] = 0; continue; }
@@ -1257,6 +1272,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       k0 += cnt;
    }
    _lastOutputKernelMs = kernelMs;
+   _lastOutputCalls = outputCalls;
    _lastOutputMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tOut0).count();
    if (_isParallelMechOrig && _isPar2Ser && _isTrqConOn) _isParallelMech = false; // reference ba.cpp:937
    int failed = 0;

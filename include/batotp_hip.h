@@ -523,11 +523,21 @@ int  batotp_hip_resampled_ms(batotp_resampled *r, float *ms);
  * the batch's chain model); BOTH paths (joint rows and pose rows, quaternions back to axis-angle at the end); and CART paths of the 3-cable robot with torque constraints (Cartesian rows,
  * cable lengths by Robot::invKinCSPR3DOF, cable tensions recomputed as in ba.cpp:1744-1790 with
  * Robot::dynCSPR3DOF / setA / solveLinSys).  The batch must have completed the forward sweep.
- * Anything else returns BATOTP_ERR_ARG (the caller keeps its host code). */
+ * Anything else returns BATOTP_ERR_ARG (the caller keeps its host code).
+ *
+ * The integration step belongs to the path (batotp_hip_set_path_integ_res).  A positive integ_res states the step of the whole
+ * range: a path that integrates with another one is refused with BATOTP_ERR_ARG.  integ_res == BATOTP_OUT_STEP_PER_PATH samples
+ * every path of the range with its own step: the effective output resolution, whether the path is re-interpolated, its smoothing
+ * factor and window, the time step of its curve, its traj.sres and the time factors of the torque recomputation are then derived
+ * per path, by the expressions a call with that path's step alone would use, and the result has the same layout (path after path).
+ * A path whose step is NaN ended its sweep with BATOTP_ST_MAX_INTEG_TIME and, like every failed path, gets n_pts = 0.  An
+ * implementation that serves one step per call only refuses the value with BATOTP_ERR_ARG: the caller keeps its loop over runs of
+ * equal step. */
+#define BATOTP_OUT_STEP_PER_PATH 0.0
 typedef struct batotp_output_params {
     int32_t  n_joints;               /* joint channels to produce (the batch's n_joints)       */
     int32_t  path_type;              /* BATOTP_PATH_JOINT (also 0) or BATOTP_PATH_CART         */
-    double   integ_res;              /* _integRes                                              */
+    double   integ_res;              /* _integRes of every path, or BATOTP_OUT_STEP_PER_PATH   */
     double   out_res;                /* _outRes                                                */
     double   out_smooth_fact;        /* _outSmoothFact                                         */
 } batotp_output_params;
