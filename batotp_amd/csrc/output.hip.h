@@ -8,26 +8,10 @@
 // builds reuse K1's Thomas code (k_spline_series, one lane per series).
 #pragma once
 #include "kernels.hip.h"
+#include "output_plan.h" // OutPath
 
 namespace bk
 {
-
-struct OutPath
-{
-   int64_t off1;    // first point of this path in the stage-1 arrays (sOut, seg, th1)
-   int64_t off2;    // ... in the down-sampled arrays (th2, sol2)
-   int64_t offF;    // ... in the final-stage arrays of the launch (dense over the paths of the launch)
-   int64_t offD;    // ... in the result of the chunk, which stays in path order (= offF unless the chunk is staged)
-   int64_t offS;    // first element of this path's s(t) second derivatives
-   int32_t p;       // path of the batch
-   int32_t nFwd;    // points of the forward curve
-   int32_t n1;      // nOut of ba.cpp:1683
-   int32_t n2;      // points after smoothing + down-sampling (= n1 without smoothing)
-   int32_t nF;      // final points
-   int32_t window;  // (int)smoothing factor of this path when it is smoothed, else 0
-   double tStep;    // time step of the forward curve (tMVC[i] = tStep*i)
-   double vfactT, afactT; // 1/tfact and its square, tfact = (output resolution)/(smoothing factor) of this path (ba.cpp:1754)
-};
 
 struct OutParams
 {

@@ -1,7 +1,7 @@
 // output_api.inc -- host side of batotp_hip_output (included at the end of batotp_hip.hip).
 // All sizes of the stage follow from the results of the forward sweep (points and time step of each curve), so
-// the host lays out every buffer before the first kernel; the paths of a call are processed in chunks whose
-// scratch fits the context's cached workspace.
+// the host lays out every buffer before the first kernel (output_plan.h); the paths of a call are processed in
+// chunks whose scratch fits the context's cached workspace.
 
 struct batotp_output
 {
@@ -63,10 +63,55 @@ extern "C" int batotp_hip_out_segmax_kat(batotp_ctx *ctx, int32_t n_paths, const
    return BATOTP_OK;
 }
 
-extern "C" int batotp_hip_output(batotp_batch *b, const batotp_output_params *prm, int32_t path0, int32_t n_paths, batotp_output **out)
+// ---- batotp_hip_output: what the call is (OutCall), one route of one chunk on the device (OutRoute), the steps of its launch
+// sequence in the order they run, and the entry point.  Every hipStreamSynchronize below guards host memory that is about to be
+// rewritten or to go out of scope; the comment beside it says which.
+
+// what every step knows about the call: the batch and which branches of the reference's stage its problem takes
+struct OutCall
 {
-   if (!b || !prm || !out || path0 < 0 || n_paths < 1 || path0 + n_paths > b->B) return BATOTP_ERR_ARG;
-   *out = nullptr;
+   batotp_batch *b;
+   batotp_ctx *ctx;
+   hipStream_t st;
+   bool cable, kin, serialTrq, both, pose, hostTrig;
+   int trigRows, nJ, nCartRows, nTrqRows;
+   int R;    // rows per point the stage works with: joints (+ Cartesian + torques)
+   int Rout; // rows per point of the result (poses leave as position + axis-angle)
+   OutParams P;
+};
+
+// the paths of one route of one chunk with their offsets (RouteLayout), the buffers carved for them from the context's workspace
+// and the host side of the series descriptors
+struct OutRoute
+{
+   RouteLayout L;
+   int Kc;
+   bool reinterp, smoothing;
+   Bump w;
+   OutPath *dPaths;
+   int64_t *dYOff, *dSOff;
+   int *dCnt, *dRedo;   // dRedo: series the wavefront-per-series solve leaves to the sequential kernel
+   double *solS, *sOut;
+   int *segK;
+   double *resultOut, *result, *th0, *sol1, *th1, *th2, *sol2;
+   std::vector<int64_t> yOff, sOff;
+   std::vector<int> cnt;
+};
+
+// scratch of the kinematics / dynamics at the output points, carved from a workspace of its own
+struct OutKin
+{
+   double *pack, *trig, *sampT, *dynT;
+   PathInfo *dFake;
+   std::vector<TrigSpan> spans;
+};
+
+constexpr int OUT_BS = 256;
+static inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + OUT_BS - 1) / OUT_BS)); }
+
+// the refusals of a call, and what it is once it is accepted; binds the context
+static int outputCall(batotp_batch *b, const batotp_output_params *prm, int32_t path0, int32_t n_paths, OutCall &c)
+{
    const bool cable = prm->path_type == BATOTP_PATH_CART && b->prob.robot_type == BATOTP_ROBOT_CSPR3DOF && prm->n_joints == 3 &&
                       b->prob.n_cart == 3 && (b->prob.flags & BATOTP_F_TRQ_ON) && (b->prob.flags & BATOTP_F_PARALLEL);
    const bool jointPath = prm->path_type == BATOTP_PATH_JOINT || prm->path_type == 0;
@@ -99,389 +144,352 @@ extern "C" int batotp_hip_output(batotp_batch *b, const batotp_output_params *pr
          return BATOTP_ERR_ARG;
       }
    }
-   const bool hostTrig = (b->prob.flags & BATOTP_F_HOST_TRIG) != 0;
    if (!b->revDone) return BATOTP_ERR_STATE;
    int rc = bind(b->ctx);
    if (rc) return rc;
-   batotp_ctx *ctx = b->ctx;
-   hipStream_t st = ctx->stream;
-   const int K = n_paths, nJ = b->P.nJ;
-   const int nCartRows = cable ? 3 : (both ? (int)b->prob.n_cart : (kin ? 3 : 0)), nTrqRows = cable ? 3 : (serialTrq ? nJ : 0);
-   const int R = nJ + nCartRows + nTrqRows; // rows per point the stage works with: joints (+ Cartesian + torques)
-   const int Rout = pose ? R - 1 : R;       // rows per point of the result (poses leave as position + axis-angle)
+   const int nJ = b->P.nJ;
+   c.b = b; c.ctx = b->ctx; c.st = b->ctx->stream;
+   c.cable = cable; c.kin = kin; c.serialTrq = serialTrq; c.both = both; c.pose = pose;
+   c.hostTrig = (b->prob.flags & BATOTP_F_HOST_TRIG) != 0;
+   c.trigRows = trigRows; c.nJ = nJ;
+   c.nCartRows = cable ? 3 : (both ? (int)b->prob.n_cart : (kin ? 3 : 0));
+   c.nTrqRows = cable ? 3 : (serialTrq ? nJ : 0);
+   c.R = nJ + c.nCartRows + c.nTrqRows;
+   c.Rout = pose ? c.R - 1 : c.R;
+   OutParams &P = c.P;
+   memset(&P, 0, sizeof(P));
+   P.nJ = nJ; P.R = c.R; P.compact = b->compact ? 1 : 0; P.kmC = b->kmC;
+   P.C = b->P.C; P.Cin = b->P.Cin; P.svd = (b->prob.flags & BATOTP_F_SVD) ? 1 : 0;
+   for (int k = 0; k < 9; ++k) P.pmat[k] = b->prob.pmat[k];
+   return BATOTP_OK;
+}
 
-   // ba.cpp:1668-1675: never sample finer than the integration step; smooth + re-interpolate afterwards.  All of it follows from
-   // the step, so it is a property of the path; `route` (re-interpolated or not, smoothed or not) decides which stages a path
-   // passes and which buffers they need.  A NaN step compares false: such a path has no forward curve and takes no route at all.
-   struct OutStep { double h, outRes, smoothFact; bool reinterp, smoothing; int route; };
-   const double outResUser = prm->out_res;
-   auto stepOf = [&](double h) {
-      OutStep s{h, prm->out_res, prm->out_smooth_fact, false, false, 0};
-      if (s.outRes < h)
+// the buffers of a route (r.L is set) from the output workspace; resultOut: the chunk's place in the result of the call
+static int carveRoute(const OutCall &c, int route, double *resultOut, OutRoute &r)
+{
+   const int R = c.R, Kc = r.Kc = (int)r.L.pc.size();
+   const int64_t t1 = r.L.t1, t2 = r.L.t2;
+   const bool reinterp = r.reinterp = (route & 2) != 0, smoothing = r.smoothing = (route & 1) != 0, torque = c.cable || c.serialTrq;
+   Bump &w = r.w;
+   w.base = (char *)c.ctx->ws[1].p;
+   r.dPaths = w.take<OutPath>(Kc);
+   r.dYOff = w.take<int64_t>((size_t)Kc * R); r.dSOff = w.take<int64_t>((size_t)Kc * R);
+   r.dCnt = w.take<int>((size_t)Kc * R);
+   r.dRedo = w.take<int>((size_t)Kc * R);
+   r.solS = w.take<double>((size_t)r.L.tS);
+   r.sOut = w.take<double>((size_t)t1);
+   r.segK = w.take<int>((size_t)t1);
+   r.resultOut = resultOut;
+   r.result = (c.pose || r.L.staged) ? w.take<double>((size_t)r.L.tF * R) : resultOut; // poses: the conversion follows the last stage
+   r.th0 = torque ? w.take<double>((size_t)t1 * R) : nullptr;  // samples before the torque step ...
+   r.sol1 = torque ? w.take<double>((size_t)t1 * R) : nullptr; // ... and the second derivatives of their splines
+   r.th1 = (smoothing || reinterp) ? w.take<double>((size_t)t1 * R) : r.result;
+   r.th2 = !smoothing ? r.th1 : (reinterp ? w.take<double>((size_t)t2 * R) : r.result);
+   r.sol2 = reinterp ? w.take<double>((size_t)t2 * R) : nullptr;
+   if (w.at > c.ctx->ws[1].cap) { snprintf(g_err, sizeof(g_err), "output stage: scratch estimate exceeded"); return BATOTP_ERR_STATE; }
+   r.yOff.resize((size_t)Kc * R); r.sOff.resize(r.yOff.size()); r.cnt.resize(r.yOff.size());
+   return BATOTP_OK;
+}
+
+// The first `series` descriptors of r.yOff / sOff / cnt to the device.  The copies read the host vectors when the stream reaches
+// them: whoever fills the vectors again synchronises first.
+static int uploadSeries(const OutCall &c, const OutRoute &r, int series)
+{
+   HIP_TRY(hipMemcpyAsync(r.dYOff, r.yOff.data(), sizeof(int64_t) * (size_t)series, hipMemcpyHostToDevice, c.st));
+   HIP_TRY(hipMemcpyAsync(r.dSOff, r.sOff.data(), sizeof(int64_t) * (size_t)series, hipMemcpyHostToDevice, c.st));
+   HIP_TRY(hipMemcpyAsync(r.dCnt, r.cnt.data(), sizeof(int) * (size_t)series, hipMemcpyHostToDevice, c.st));
+   return BATOTP_OK;
+}
+
+// ... of the first `rows` channels of every path, solved in place: a path's points are an [R][n] block of the stage-1 arrays
+// (down == false) or of the down-sampled ones
+static int uploadChannelSeries(const OutCall &c, OutRoute &r, int rows, bool down)
+{
+   for (int k = 0; k < r.Kc; ++k)
+   {
+      const OutPath &q = r.L.pc[k];
+      const int64_t off = down ? q.off2 : q.off1;
+      const int n = down ? q.n2 : q.n1;
+      for (int ch = 0; ch < rows; ++ch)
       {
-         s.reinterp = true;
-         s.outRes = h;
-         s.smoothFact *= std::max(outResUser / s.outRes, 1.);
+         const size_t at = (size_t)k * rows + ch;
+         r.yOff[at] = off * c.R + (int64_t)ch * n;
+         r.sOff[at] = r.yOff[at];
+         r.cnt[at] = n;
       }
-      s.smoothing = s.smoothFact > 1.5;
-      s.route = (s.reinterp ? 2 : 0) | (s.smoothing ? 1 : 0);
-      return s;
-   };
-   std::vector<OutStep> step(K);
-   for (int k = 0; k < K; ++k) step[k] = stepOf(perPath ? b->pinfo[path0 + k].integ_res : prm->integ_res);
+   }
+   return uploadSeries(c, r, r.Kc * rows);
+}
+
+// natural-spline second derivatives of `series` series (the descriptors on the device): a wavefront per series where the series
+// is long enough (spline_lanes.hip.h) and there are few of them (seriesLanesPay), the lane-per-series kernel for the rest
+static void solveSeries(const OutCall &c, const OutRoute &r, int series, const double *y, int ys, double *sol)
+{
+   const bool byLanes = seriesLanesPay(series);
+   if (byLanes) hipLaunchKernelGGL(k_spline_series_lanes, dim3((unsigned)series), dim3(64), 0, c.st, series, r.dYOff, r.dSOff, r.dCnt, y, ys, sol, r.dRedo);
+   const unsigned lanes = seriesBlock(series);
+   hipLaunchKernelGGL(k_spline_series, dim3((unsigned)((series + lanes - 1) / lanes)), dim3(lanes), 0, c.st, series, r.dYOff, r.dSOff, r.dCnt, y, ys, sol,
+                      byLanes ? r.dRedo : nullptr);
+}
+
+// s at the output times of every path and the segment of the path spline each falls into (ba.cpp:1683-1707)
+static int sampleS(const OutCall &c, OutRoute &r)
+{
+   batotp_batch *b = c.b;
+   for (int k = 0; k < r.Kc; ++k)
+   {
+      const OutPath &q = r.L.pc[k];
+      r.yOff[k] = (int64_t)q.p * b->cap * 2; // s of point i of the forward curve = element 2*i of its slot
+      r.sOff[k] = q.offS;
+      r.cnt[k] = q.nFwd;
+   }
+   HIP_TRY(hipMemcpyAsync(r.dPaths, r.L.pc.data(), sizeof(OutPath) * r.Kc, hipMemcpyHostToDevice, c.st));
+   int rc = uploadSeries(c, r, r.Kc);
+   if (rc) return rc;
+   solveSeries(c, r, r.Kc, reinterpret_cast<const double *>(b->dFwd), 2, r.solS);
+   hipLaunchKernelGGL(k_out_s, grid256(r.L.t1), dim3(OUT_BS), 0, c.st, r.dPaths, r.Kc, b->dFwd, b->cap, r.solS, b->dPinfo, b->dSC, r.sOut, r.segK, r.L.t1);
+   launchOutSegmax(c.st, r.dPaths, r.Kc, r.segK);
+   return BATOTP_OK;
+}
+
+// joint rows (already packed on the device) -> host -> trig table -> device
+// (the tables are trigonometric functions of the joint rows alone: neither this nor hostTrigTables reads a step)
+static int tableFor(const OutCall &c, const OutRoute &r, const OutKin &kn, int kind, double unit)
+{
+   batotp_ctx *ctx = c.ctx;
+   const int rows = hostTrigRows(kind, c.b->prob.robot_type, c.nJ);
+   ctx->kinTheta.resize((size_t)r.L.t1 * c.nJ);
+   ctx->kinTrig.resize((size_t)r.L.t1 * rows);
+   HIP_TRY(hipMemcpyAsync(ctx->kinTheta.data(), kn.pack, sizeof(double) * ctx->kinTheta.size(), hipMemcpyDeviceToHost, c.st));
+   HIP_TRY(hipStreamSynchronize(c.st));
+   hostTrigTables(kind, c.b->prob.robot_type, c.nJ, unit, kn.spans, ctx->kinTheta.data(), ctx->kinTrig.data());
+   HIP_TRY(hipMemcpyAsync(kn.trig, ctx->kinTrig.data(), sizeof(double) * ctx->kinTrig.size(), hipMemcpyHostToDevice, c.st));
+   HIP_TRY(hipStreamSynchronize(c.st)); // the host table is reused
+   return BATOTP_OK;
+}
+
+// ba.cpp:1791-1827: clamped splines through the joint samples, value / derivatives at the end of the previous segment,
+// Robot::dynSerial there (the batch's own kernels on a sample array of the output points), a2 + a3 + a4
+static int serialTorque(const OutCall &c, OutRoute &r, const OutKin &kn)
+{
+   batotp_batch *b = c.b;
+   hipStream_t st = c.st;
+   const int Kc = r.Kc, nJ = c.nJ;
+   const int64_t t1 = r.L.t1;
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
+   std::vector<PathInfo> fake(Kc);
+   for (int k = 0; k < Kc; ++k)
+   {
+      memset(&fake[k], 0, sizeof(PathInfo));
+      fake[k].koff = r.L.pc[k].off1; fake[k].n = r.L.pc[k].n1;
+   }
+   HIP_TRY(hipMemcpyAsync(kn.dFake, fake.data(), sizeof(PathInfo) * (size_t)Kc, hipMemcpyHostToDevice, st));
+   int rc = uploadChannelSeries(c, r, nJ, false);
+   if (rc) return rc;
+   hipLaunchKernelGGL(k_spline_series_clamped, dim3((unsigned)((Kc * nJ + seriesBlock(Kc * nJ) - 1) / seriesBlock(Kc * nJ))), dim3(seriesBlock(Kc * nJ)), 0, st, Kc * nJ, r.dYOff, r.dSOff, r.dCnt, r.th0, r.sol1);
+   HIP_TRY(hipMemsetAsync(kn.sampT, 0, sizeof(double) * (size_t)t1 * 3 * b->P.Cin, st));
+   hipLaunchKernelGGL(k_out_serial_eval, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, r.th0, r.sol1, r.th1, kn.sampT, kn.pack, c.nCartRows, t1);
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipStreamSynchronize(st)); // `fake` leaves scope below; the trig tables follow
+   const double *trigDyn = nullptr;
+   if (c.hostTrig)
+   {
+      const double unit = (b->hasSerial && b->hModel.degrees) ? KIN_DEG2RAD : 1.0;
+      if ((rc = tableFor(c, r, kn, b->hasSerial ? 2 : 1, unit))) return rc;
+      trigDyn = kn.trig;
+   }
+   if (b->hasSerial)
+      hipLaunchKernelGGL(k_dyn_serial, dim3((unsigned)((t1 + KDS_BLOCK - 1) / KDS_BLOCK)), dim3(KDS_BLOCK), 0, st, b->dModel, b->P.Cin, kn.dFake, Kc,
+                         kn.sampT, trigDyn, kn.dynT, t1);
+   else
+      hipLaunchKernelGGL(k_dynamics, grid256(t1), dim3(OUT_BS), 0, st, b->P, b->dP, kn.dFake, Kc, kn.sampT, trigDyn, kn.dynT, t1);
+   hipLaunchKernelGGL(k_out_trq_sum, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, kn.dynT, r.th1, nJ + c.nCartRows, t1);
+   return BATOTP_OK;
+}
+
+// JOINT and BOTH paths: the rows from the path splines, then the forward kinematics and the torques of a serial robot
+static int evalJoints(const OutCall &c, OutRoute &r)
+{
+   batotp_batch *b = c.b;
+   batotp_ctx *ctx = c.ctx;
+   hipStream_t st = c.st;
+   const int Kc = r.Kc, nJ = c.nJ;
+   const int64_t t1 = r.L.t1;
+   double *thA = c.serialTrq ? r.th0 : r.th1; // joint (and Cartesian) rows before the torque step
+   hipLaunchKernelGGL(k_out_eval, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM, r.sOut, r.segK, thA, 0, nJ, 0, t1);
+   if (c.both)   // the Cartesian rows from their splines, like the joints (ba.cpp:1726-1736)
+      hipLaunchKernelGGL(k_out_eval, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM, r.sOut, r.segK, thA, nJ, c.nCartRows, nJ, t1);
+   if (!c.kin && !c.serialTrq) return BATOTP_OK;
+   // scratch of the kinematics / dynamics at the output points (own workspace): packed joint rows, trig table, and for
+   // the torque step a sample array [Cin][3][n1], a dynamics array [4][nJ][n1] and the PathInfo rows k_dynamics reads
+   const int rowsDyn = c.serialTrq ? (b->hasSerial ? 2 * nJ : 4) : 0;
+   const int rowsT = std::max(c.kin ? c.trigRows : 0, rowsDyn);
+   const size_t needKin = 8 * (size_t)t1 * (size_t)(nJ + rowsT + (c.serialTrq ? 3 * b->P.Cin + 4 * nJ : 0)) + sizeof(PathInfo) * (size_t)Kc + 4096;
+   int rc;
+   if ((rc = arenaReserve(ctx->ws[3], needKin, st))) return rc;
+   if ((rc = poisonFill(ctx, ctx->ws[3].p, ctx->ws[3].cap, st))) return rc;
+   Bump wk;
+   wk.base = (char *)ctx->ws[3].p;
+   OutKin kn;
+   kn.pack = wk.take<double>((size_t)t1 * nJ); kn.trig = wk.take<double>((size_t)t1 * rowsT);
+   kn.sampT = c.serialTrq ? wk.take<double>((size_t)t1 * 3 * b->P.Cin) : nullptr;
+   kn.dynT = c.serialTrq ? wk.take<double>((size_t)t1 * 4 * nJ) : nullptr;
+   kn.dFake = wk.take<PathInfo>((size_t)Kc);
+   kn.spans.resize(Kc);
+   for (int k = 0; k < Kc; ++k) kn.spans[k] = TrigSpan{r.L.pc[k].off1, r.L.pc[k].n1, r.L.pc[k].n1 == 0};
+   if (c.kin)
+   {
+      // Robot::fwdKin at the output points, ba.cpp:1722-1725
+      if (c.hostTrig)
+      {
+         hipLaunchKernelGGL(k_out_pack_theta, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, thA, kn.pack, t1);
+         if ((rc = tableFor(c, r, kn, 0, 1.0))) return rc;
+      }
+      hipLaunchKernelGGL(k_out_fwdkin, grid256(t1), dim3(OUT_BS), 0, st, c.P, b->prob.robot_type, r.dPaths, Kc, thA,
+                         c.hostTrig ? kn.trig : (const double *)nullptr, c.trigRows, b->dPinfo, b->dSamp, t1);
+   }
+   return c.serialTrq ? serialTorque(c, r, kn) : BATOTP_OK;
+}
+
+// CART path of the cable robot: Cartesian rows from the path splines, cable lengths from them, then the torque step
+static int evalCable(const OutCall &c, OutRoute &r)
+{
+   batotp_batch *b = c.b;
+   hipStream_t st = c.st;
+   const int64_t t1 = r.L.t1;
+   hipLaunchKernelGGL(k_out_eval, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, r.Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM, r.sOut, r.segK, r.th0, c.nJ, 3, 3, t1);
+   hipLaunchKernelGGL(k_out_invkin, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, r.Kc, r.th0, t1);
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
+   int rc = uploadChannelSeries(c, r, 6, false);
+   if (rc) return rc;
+   solveSeries(c, r, r.Kc * 6, r.th0, 1, r.sol1);
+   hipLaunchKernelGGL(k_out_trq, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, r.Kc, r.th0, r.sol1, r.th1, t1);
+   return BATOTP_OK;
+}
+
+// BA::q2aaVect (ba.cpp:1920-1927): quaternion rows -> axis-angle rows, the result loses the seventh Cartesian row
+static int poseToAxisAngle(const OutCall &c, OutRoute &r)
+{
+   batotp_ctx *ctx = c.ctx;
+   hipStream_t st = c.st;
+   const int64_t tF = r.L.tF;
+   const double *atDev = nullptr;
+   if (c.hostTrig)
+   {
+      double *packQ = r.w.take<double>((size_t)tF * 2), *atTab = r.w.take<double>((size_t)tF);
+      if (r.w.at > ctx->ws[1].cap) { snprintf(g_err, sizeof(g_err), "output stage: scratch estimate exceeded"); return BATOTP_ERR_STATE; }
+      hipLaunchKernelGGL(k_out_q_norm, grid256(tF), dim3(OUT_BS), 0, st, c.nJ, c.R, r.dPaths, r.Kc, r.result, packQ, tF);
+      ctx->kinTheta.resize((size_t)tF * 2);
+      ctx->kinTrig.resize((size_t)tF);
+      HIP_TRY(hipMemcpyAsync(ctx->kinTheta.data(), packQ, sizeof(double) * (size_t)tF * 2, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      for (const OutPath &q : r.L.pc)
+      {
+         const int64_t off = q.offF, n = q.nF;
+         for (int64_t i = 0; i < n; ++i)   // util.cpp:573: one atan2() per point, host libm
+            ctx->kinTrig[(size_t)(off + i)] = ::atan2(ctx->kinTheta[(size_t)(off * 2 + i)], ctx->kinTheta[(size_t)(off * 2 + n + i)]);
+      }
+      HIP_TRY(hipMemcpyAsync(atTab, ctx->kinTrig.data(), sizeof(double) * (size_t)tF, hipMemcpyHostToDevice, st));
+      atDev = atTab;
+   }
+   hipLaunchKernelGGL(k_out_q2aa, grid256(tF), dim3(OUT_BS), 0, st, c.nJ, c.R, r.dPaths, r.Kc, r.result, atDev, r.resultOut, tF);
+   HIP_TRY(hipGetLastError());
+   return BATOTP_OK;
+}
+
+// smoothing + down-sampling, re-interpolation at the user's resolution, and the rows into their place in the result
+static int finishRoute(const OutCall &c, OutRoute &r)
+{
+   hipStream_t st = c.st;
+   const int64_t tF = r.L.tF;
+   if (r.smoothing) hipLaunchKernelGGL(k_out_down, grid256(r.L.t2), dim3(OUT_BS), 0, st, c.P, r.dPaths, r.Kc, r.th1, r.th2, r.L.t2);
+   HIP_TRY(hipGetLastError());
+   if (r.reinterp)
+   {
+      HIP_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
+      int rc = uploadChannelSeries(c, r, c.R, true);
+      if (rc) return rc;
+      solveSeries(c, r, r.Kc * c.R, r.th2, 1, r.sol2);
+      hipLaunchKernelGGL(k_out_user, grid256(tF), dim3(OUT_BS), 0, st, c.P, r.dPaths, r.Kc, r.th2, r.sol2, r.result, tF);
+      HIP_TRY(hipGetLastError());
+   }
+   if (c.pose) return poseToAxisAngle(c, r);
+   if (r.L.staged)
+   {
+      hipLaunchKernelGGL(k_out_place, grid256(tF), dim3(OUT_BS), 0, st, c.R, r.dPaths, r.Kc, r.result, r.resultOut, tF);
+      HIP_TRY(hipGetLastError());
+   }
+   return BATOTP_OK;
+}
+
+extern "C" int batotp_hip_output(batotp_batch *b, const batotp_output_params *prm, int32_t path0, int32_t n_paths, batotp_output **out)
+{
+   if (!b || !prm || !out || path0 < 0 || n_paths < 1 || path0 + n_paths > b->B) return BATOTP_ERR_ARG;
+   *out = nullptr;
+   OutCall c;
+   int rc = outputCall(b, prm, path0, n_paths, c);
+   if (rc) return rc;
+   batotp_ctx *ctx = c.ctx;
+   hipStream_t st = c.st;
+   const int K = n_paths;
 
    std::vector<batotp_path_result> res(b->B);
    HIP_TRY(hipMemcpyAsync(res.data(), b->dRes, sizeof(batotp_path_result) * b->B, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipStreamSynchronize(st));
 
-   batotp_output *o = new (std::nothrow) batotp_output;
+   std::vector<double> h(K);
+   for (int k = 0; k < K; ++k) h[k] = prm->integ_res == BATOTP_OUT_STEP_PER_PATH ? b->pinfo[path0 + k].integ_res : prm->integ_res;
+   OutPlan pl;
+   planOutput(res.data() + path0, h.data(), K, path0, prm->out_res, prm->out_smooth_fact, pl);
+
+   struct Owner { batotp_output *o; ~Owner() { batotp_hip_output_destroy(o); } } own{new (std::nothrow) batotp_output};
+   batotp_output *o = own.o;
    if (!o) return BATOTP_ERR_ALLOC;
-   o->ctx = ctx; o->K = K; o->nJ = Rout; o->nTheta = nJ; o->nCart = pose ? 6 : nCartRows; o->nTrq = nTrqRows;
-   o->n.assign(K, 0); o->off.assign(K, 0); o->sres.assign(K, 0.0);
-   std::vector<OutPath> all(K);
-   int64_t totF = 0;
-   unsigned routesLive = 0; // routes taken by the paths of the range that have a trajectory
-   for (int k = 0; k < K; ++k)
-   {
-      OutPath &q = all[k];
-      const OutStep &S = step[k];
-      const double outRes = S.outRes, smoothFact = S.smoothFact;
-      const bool reinterp = S.reinterp, smoothing = S.smoothing;
-      memset(&q, 0, sizeof(q));
-      const batotp_path_result &r = res[path0 + k];
-      const uint32_t stt = r.status_rev | r.status_fwd;
-      q.p = path0 + k;
-      q.offF = totF;
-      o->off[k] = totF;
-      if (r.n_fwd < 4 || !(S.h > 0) || (stt & (BATOTP_ST_MAX_INTEG_TIME | BATOTP_ST_CAPACITY | BATOTP_ST_NONFINITE))) continue;
-      q.nFwd = (int32_t)r.n_fwd;
-      q.tStep = (r.status_fwd & BATOTP_ST_SHORT) ? r.t_total / 3. : S.h;
-      const double tLast = q.tStep * (double)(q.nFwd - 1);
-      int nOut = (int)(smoothFact * std::ceil(tLast / outRes + 1.)); // ba.cpp:1683
-      nOut = std::max(nOut, 4);
-      q.n1 = nOut;
-      q.n2 = smoothing ? std::max((int)((nOut - 1) / smoothFact) + 1, 4) : nOut; // ba.cpp:1841
-      q.nF = reinterp ? std::max((int)(std::ceil(tLast / outResUser)), 4) : q.n2;  // ba.cpp:1876
-      o->n[k] = q.nF;
-      o->sres[k] = reinterp ? outResUser : outRes;
-      q.window = smoothing ? (int)smoothFact : 0;
-      const double tfact = outRes / smoothFact; // traj.sres/_outSmoothFact, ba.cpp:1754
-      q.vfactT = 1.0 / tfact;
-      q.afactT = q.vfactT * q.vfactT;
-      routesLive |= 1u << S.route;
-      totF += q.nF;
-   }
-   // more than one route in the range: the chunks that mix them stage their results (see the chunk loop)
-   const bool mixedCall = (routesLive & (routesLive - 1)) != 0;
-   o->total = totF;
-   hipError_t e = hipMalloc((void **)&o->dTheta, sizeof(double) * (size_t)std::max<int64_t>(totF * Rout, 1));
+   o->ctx = ctx; o->K = K; o->nJ = c.Rout; o->nTheta = c.nJ; o->nCart = c.pose ? 6 : c.nCartRows; o->nTrq = c.nTrqRows;
+   o->n = pl.n; o->off = pl.off; o->sres = pl.sres;
+   o->total = pl.totF;
+   const size_t resultBytes = sizeof(double) * (size_t)std::max<int64_t>(pl.totF * c.Rout, 1);
+   hipError_t e = hipMalloc((void **)&o->dTheta, resultBytes);
    if (e != hipSuccess)
    {
-      delete o;
       hipFail(e, "hipMalloc (output trajectories)");
       (void)hipGetLastError(); // reported; clear the sticky error
       return BATOTP_ERR_ALLOC;
    }
-   if ((rc = poisonFill(ctx, o->dTheta, sizeof(double) * (size_t)std::max<int64_t>(totF * Rout, 1), st))) { batotp_hip_output_destroy(o); return rc; }
+   if ((rc = poisonFill(ctx, o->dTheta, resultBytes, st))) return rc;
 
-   OutParams P;
-   memset(&P, 0, sizeof(P));
-   P.nJ = nJ; P.R = R; P.compact = b->compact ? 1 : 0; P.kmC = b->kmC;
-   P.C = b->P.C; P.Cin = b->P.Cin; P.svd = (b->prob.flags & BATOTP_F_SVD) ? 1 : 0;
-   for (int k = 0; k < 9; ++k) P.pmat[k] = b->prob.pmat[k];
-
-   // scratch of one path: s(t) second derivatives | sOut, segment | th1 (unless final) | th2 (if a middle stage) | sol2
-   auto scratchOf = [&](const OutPath &q, const OutStep &S) -> size_t {
-      const bool smoothing = S.smoothing, reinterp = S.reinterp;
-      size_t by = 8 * (size_t)q.nFwd + 12 * (size_t)q.n1 + 8 * 256 + sizeof(OutPath) + 2 * sizeof(int64_t) * (1 + R) + 2 * sizeof(int) * (1 + R);
-      if (smoothing || reinterp) by += 8 * (size_t)R * q.n1;
-      if (smoothing && reinterp) by += 8 * (size_t)R * q.n2;
-      if (reinterp) by += 8 * (size_t)R * q.n2;
-      if (cable || serialTrq) by += 2 * 8 * (size_t)R * q.n1; // samples before the torque step and their second derivatives
-      if (pose) by += 8 * (size_t)(R + 3) * q.nF + 1024;      // final rows before the pose conversion, (norm, q0) pairs, atan2 table
-      else if (mixedCall) by += 8 * (size_t)R * q.nF;         // staged final rows of a chunk that mixes routes
-      return by;
-   };
    size_t freeB = 0, totalB = 0;
    hipMemGetInfo(&freeB, &totalB);
    double budget = std::min(0.5 * (double)(freeB + ctx->ws[1].cap), 24.0 * 1073741824.0);
    if (ctx->outBudget > 0) budget = (double)ctx->outBudget; // batotp_hip_set_workspace_budget
-   std::vector<int> cuts(1, 0);
-   size_t maxChunk = 0;
-   {
-      size_t bytes = 0;
-      for (int k = 0; k < K; ++k)
-      {
-         const size_t need = scratchOf(all[k], step[k]);
-         if (k > cuts.back() && (double)(bytes + need) > budget) { cuts.push_back(k); bytes = 0; }
-         bytes += need;
-         maxChunk = std::max(maxChunk, bytes);
-      }
-      cuts.push_back(K);
-   }
-#define OUT_TRY(call)                                                              \
-   do                                                                              \
-   {                                                                               \
-      hipError_t e_ = (call);                                                      \
-      if (e_ != hipSuccess) { batotp_hip_output_destroy(o); return hipFail(e_, #call); } \
-   } while (0)
-   if ((rc = arenaReserve(ctx->ws[1], maxChunk + 4096, st))) { batotp_hip_output_destroy(o); return rc; }
-   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-   OUT_TRY(hipEventCreate(&ev0));
-   OUT_TRY(hipEventCreate(&ev1));
-   struct EvGuard { hipEvent_t a, b; ~EvGuard() { hipEventDestroy(a); hipEventDestroy(b); } } evGuard{ev0, ev1};
-   OUT_TRY(hipEventRecord(ev0, st));
-   const int bs = 256;
-   // natural-spline second derivatives of `series` series (descriptors in dYOff / dSOff / dCnt): a wavefront per series where the
-   // series is long enough (spline_lanes.hip.h) and there are few of them (seriesLanesPay), the lane-per-series kernel for the rest
-   auto solveSeries = [&](int series, const int64_t *dYOff, const int64_t *dSOff, const int *dCnt, int *dRedo, const double *y, int ys, double *sol) {
-      const bool byLanes = seriesLanesPay(series);
-      if (byLanes) hipLaunchKernelGGL(k_spline_series_lanes, dim3((unsigned)series), dim3(64), 0, st, series, dYOff, dSOff, dCnt, y, ys, sol, dRedo);
-      const unsigned lanes = seriesBlock(series);
-      hipLaunchKernelGGL(k_spline_series, dim3((unsigned)((series + lanes - 1) / lanes)), dim3(lanes), 0, st, series, dYOff, dSOff, dCnt, y, ys, sol,
-                         byLanes ? dRedo : nullptr);
-   };
+   cutChunks(pl, OutRows{c.R, c.cable || c.serialTrq, c.pose}, budget);
+   if ((rc = arenaReserve(ctx->ws[1], pl.maxChunk + 4096, st))) return rc;
+   struct Event { hipEvent_t e = nullptr; ~Event() { if (e) hipEventDestroy(e); } } ev0, ev1;
+   HIP_TRY(hipEventCreate(&ev0.e));
+   HIP_TRY(hipEventCreate(&ev1.e));
+   HIP_TRY(hipEventRecord(ev0.e, st));
 
-   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci)
-   {
-      const int ka = cuts[ci], kb = cuts[ci + 1];
-      const int64_t baseF = all[ka].offF;
-      // The paths of a chunk run route by route through one launch sequence each: at most four, whatever the number of paths and
-      // however their routes alternate.  Within a sequence every offset is dense over its own paths (out_find_path searches them);
-      // offD is the path's place in the result, which stays in path order.  Where a chunk holds one route only (always, with a
-      // positive integ_res) the two coincide and the last stage writes the result itself, as it always did; a chunk that mixes
-      // routes stages the final rows of each sequence and k_out_place moves them.
-      unsigned routesChunk = 0;
-      for (int k = ka; k < kb; ++k) if (all[k].nFwd) routesChunk |= 1u << step[k].route;
-      const bool staged = (routesChunk & (routesChunk - 1)) != 0;
+   for (size_t ci = 0; ci + 1 < pl.cuts.size(); ++ci)
       for (int route = 0; route < 4; ++route)
       {
-         const bool reinterp = (route & 2) != 0, smoothing = (route & 1) != 0;
-         std::vector<OutPath> pc;
-         for (int k = ka; k < kb; ++k) if (step[k].route == route) pc.push_back(all[k]);
-         const int Kc = (int)pc.size();
-         int64_t t1 = 0, t2 = 0, tS = 0, tF = 0;
-         for (OutPath &q : pc)
-         {
-            q.off1 = t1; q.off2 = t2; q.offS = tS; q.offD = q.offF - baseF; q.offF = tF;
-            t1 += q.n1; t2 += q.n2; tS += q.nFwd; tF += q.nF;
-         }
-         if (t1 == 0) continue; // no path of the chunk takes this route, or every one that would failed in the sweep
-         if (!smoothing) for (OutPath &q : pc) q.off2 = q.off1;
-
-         if ((rc = poisonFill(ctx, ctx->ws[1].p, ctx->ws[1].cap, st))) { batotp_hip_output_destroy(o); return rc; }   // (every chunk starts from poisoned scratch)
-         Bump w;
-         w.base = (char *)ctx->ws[1].p;
-         OutPath *dPaths = w.take<OutPath>(Kc);
-         int64_t *dYOff = w.take<int64_t>((size_t)Kc * R), *dSOff = w.take<int64_t>((size_t)Kc * R);
-         int *dCnt = w.take<int>((size_t)Kc * R);
-         int *dRedo = w.take<int>((size_t)Kc * R); // series the wavefront-per-series solve leaves to the sequential kernel
-         double *solS = w.take<double>((size_t)tS);
-         double *sOut = w.take<double>((size_t)t1);
-         int *segK = w.take<int>((size_t)t1);
-         double *resultOut = o->dTheta + baseF * Rout;
-         double *result = (pose || staged) ? w.take<double>((size_t)tF * R) : resultOut;   // poses: the conversion follows the last stage
-         double *th0 = (cable || serialTrq) ? w.take<double>((size_t)t1 * R) : nullptr;  // samples before the torque step ...
-         double *sol1 = (cable || serialTrq) ? w.take<double>((size_t)t1 * R) : nullptr; // ... and the second derivatives of their splines
-         double *th1 = (smoothing || reinterp) ? w.take<double>((size_t)t1 * R) : result;
-         double *th2 = !smoothing ? th1 : (reinterp ? w.take<double>((size_t)t2 * R) : result);
-         double *sol2 = reinterp ? w.take<double>((size_t)t2 * R) : nullptr;
-         if (w.at > ctx->ws[1].cap) { batotp_hip_output_destroy(o); snprintf(g_err, sizeof(g_err), "output stage: scratch estimate exceeded"); return BATOTP_ERR_STATE; }
-
-         // series descriptors: s(t) of every path, then (re-interpolation) every channel of every path
-         std::vector<int64_t> yOff((size_t)Kc * R), sOff(yOff.size());
-         std::vector<int> cnt(yOff.size());
-         for (int k = 0; k < Kc; ++k)
-         {
-            yOff[k] = (int64_t)pc[k].p * b->cap * 2; // s of point i of the forward curve = element 2*i of its slot
-            sOff[k] = pc[k].offS;
-            cnt[k] = pc[k].nFwd;
-         }
-         OUT_TRY(hipMemcpyAsync(dPaths, pc.data(), sizeof(OutPath) * Kc, hipMemcpyHostToDevice, st));
-         OUT_TRY(hipMemcpyAsync(dYOff, yOff.data(), sizeof(int64_t) * Kc, hipMemcpyHostToDevice, st));
-         OUT_TRY(hipMemcpyAsync(dSOff, sOff.data(), sizeof(int64_t) * Kc, hipMemcpyHostToDevice, st));
-         OUT_TRY(hipMemcpyAsync(dCnt, cnt.data(), sizeof(int) * Kc, hipMemcpyHostToDevice, st));
-         solveSeries(Kc, dYOff, dSOff, dCnt, dRedo, reinterpret_cast<const double *>(b->dFwd), 2, solS);
-         hipLaunchKernelGGL(k_out_s, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, dPaths, Kc, b->dFwd, b->cap, solS, b->dPinfo, b->dSC, sOut,
-                            segK, t1);
-         launchOutSegmax(st, dPaths, Kc, segK);
-         if (!cable)
-         {
-            double *thA = serialTrq ? th0 : th1; // joint (and Cartesian) rows before the torque step
-            hipLaunchKernelGGL(k_out_eval, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM,
-                               sOut, segK, thA, 0, nJ, 0, t1);
-            if (both)   // the Cartesian rows from their splines, like the joints (ba.cpp:1726-1736)
-               hipLaunchKernelGGL(k_out_eval, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM,
-                                  sOut, segK, thA, nJ, nCartRows, nJ, t1);
-            if (kin || serialTrq)
-            {
-               // scratch of the kinematics / dynamics at the output points (own workspace): packed joint rows, trig table, and for
-               // the torque step a sample array [Cin][3][n1], a dynamics array [4][nJ][n1] and the PathInfo rows k_dynamics reads
-               const int rowsDyn = serialTrq ? (b->hasSerial ? 2 * nJ : 4) : 0;
-               const int rowsT = std::max(kin ? trigRows : 0, rowsDyn);
-               const size_t needKin = 8 * (size_t)t1 * (size_t)(nJ + rowsT + (serialTrq ? 3 * b->P.Cin + 4 * nJ : 0)) + sizeof(PathInfo) * (size_t)Kc + 4096;
-               if ((rc = arenaReserve(ctx->ws[3], needKin, st))) { batotp_hip_output_destroy(o); return rc; }
-               if ((rc = poisonFill(ctx, ctx->ws[3].p, ctx->ws[3].cap, st))) { batotp_hip_output_destroy(o); return rc; }
-               Bump wk;
-               wk.base = (char *)ctx->ws[3].p;
-               double *pack = wk.take<double>((size_t)t1 * nJ), *trig = wk.take<double>((size_t)t1 * rowsT);
-               double *sampT = serialTrq ? wk.take<double>((size_t)t1 * 3 * b->P.Cin) : nullptr;
-               double *dynT = serialTrq ? wk.take<double>((size_t)t1 * 4 * nJ) : nullptr;
-               PathInfo *dFake = wk.take<PathInfo>((size_t)Kc);
-               std::vector<TrigSpan> spans(Kc);
-               for (int k = 0; k < Kc; ++k) spans[k] = TrigSpan{pc[k].off1, pc[k].n1, pc[k].n1 == 0};
-               const unsigned grid1 = (unsigned)((t1 + bs - 1) / bs);
-               // (the tables are trigonometric functions of the joint rows alone: neither tableFor nor hostTrigTables reads a step)
-               auto tableFor = [&](int kind, double unit) -> int {
-                  // joint rows (already packed on the device) -> host -> trig table -> device
-                  const int rows = hostTrigRows(kind, b->prob.robot_type, nJ);
-                  ctx->kinTheta.resize((size_t)t1 * nJ);
-                  ctx->kinTrig.resize((size_t)t1 * rows);
-                  HIP_TRY(hipMemcpyAsync(ctx->kinTheta.data(), pack, sizeof(double) * ctx->kinTheta.size(), hipMemcpyDeviceToHost, st));
-                  HIP_TRY(hipStreamSynchronize(st));
-                  hostTrigTables(kind, b->prob.robot_type, nJ, unit, spans, ctx->kinTheta.data(), ctx->kinTrig.data());
-                  HIP_TRY(hipMemcpyAsync(trig, ctx->kinTrig.data(), sizeof(double) * ctx->kinTrig.size(), hipMemcpyHostToDevice, st));
-                  HIP_TRY(hipStreamSynchronize(st)); // the host table is reused
-                  return BATOTP_OK;
-               };
-               if (kin)
-               {
-                  // Robot::fwdKin at the output points, ba.cpp:1722-1725
-                  if (hostTrig)
-                  {
-                     hipLaunchKernelGGL(k_out_pack_theta, dim3(grid1), dim3(bs), 0, st, P, dPaths, Kc, thA, pack, t1);
-                     if ((rc = tableFor(0, 1.0))) { batotp_hip_output_destroy(o); return rc; }
-                  }
-                  hipLaunchKernelGGL(k_out_fwdkin, dim3(grid1), dim3(bs), 0, st, P, b->prob.robot_type, dPaths, Kc, thA,
-                                     hostTrig ? trig : (const double *)nullptr, trigRows, b->dPinfo, b->dSamp, t1);
-               }
-               if (serialTrq)
-               {
-                  // ba.cpp:1791-1827: clamped splines through the joint samples, value / derivatives at the end of the previous
-                  // segment, Robot::dynSerial there (the batch's own kernels on a sample array of the output points), a2 + a3 + a4
-                  OUT_TRY(hipGetLastError());
-                  OUT_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
-                  std::vector<PathInfo> fake(Kc);
-                  for (int k = 0; k < Kc; ++k)
-                  {
-                     memset(&fake[k], 0, sizeof(PathInfo));
-                     fake[k].koff = pc[k].off1; fake[k].n = pc[k].n1;
-                     for (int c = 0; c < nJ; ++c)
-                     {
-                        const size_t at = (size_t)k * nJ + c;
-                        yOff[at] = pc[k].off1 * R + (int64_t)c * pc[k].n1;
-                        sOff[at] = yOff[at];
-                        cnt[at] = pc[k].n1;
-                     }
-                  }
-                  OUT_TRY(hipMemcpyAsync(dFake, fake.data(), sizeof(PathInfo) * (size_t)Kc, hipMemcpyHostToDevice, st));
-                  OUT_TRY(hipMemcpyAsync(dYOff, yOff.data(), sizeof(int64_t) * (size_t)Kc * nJ, hipMemcpyHostToDevice, st));
-                  OUT_TRY(hipMemcpyAsync(dSOff, sOff.data(), sizeof(int64_t) * (size_t)Kc * nJ, hipMemcpyHostToDevice, st));
-                  OUT_TRY(hipMemcpyAsync(dCnt, cnt.data(), sizeof(int) * (size_t)Kc * nJ, hipMemcpyHostToDevice, st));
-                  hipLaunchKernelGGL(k_spline_series_clamped, dim3((unsigned)((Kc * nJ + seriesBlock(Kc * nJ) - 1) / seriesBlock(Kc * nJ))), dim3(seriesBlock(Kc * nJ)), 0, st, Kc * nJ, dYOff, dSOff, dCnt, th0, sol1);
-                  OUT_TRY(hipMemsetAsync(sampT, 0, sizeof(double) * (size_t)t1 * 3 * b->P.Cin, st));
-                  hipLaunchKernelGGL(k_out_serial_eval, dim3(grid1), dim3(bs), 0, st, P, dPaths, Kc, th0, sol1, th1, sampT, pack, nCartRows, t1);
-                  OUT_TRY(hipGetLastError());
-                  OUT_TRY(hipStreamSynchronize(st)); // `fake` leaves scope below; the trig tables follow
-                  const double *trigDyn = nullptr;
-                  if (hostTrig)
-                  {
-                     const double unit = (b->hasSerial && b->hModel.degrees) ? KIN_DEG2RAD : 1.0;
-                     if ((rc = tableFor(b->hasSerial ? 2 : 1, unit))) { batotp_hip_output_destroy(o); return rc; }
-                     trigDyn = trig;
-                  }
-                  if (b->hasSerial)
-                     hipLaunchKernelGGL(k_dyn_serial, dim3((unsigned)((t1 + KDS_BLOCK - 1) / KDS_BLOCK)), dim3(KDS_BLOCK), 0, st, b->dModel, b->P.Cin, dFake, Kc,
-                                        sampT, trigDyn, dynT, t1);
-                  else
-                     hipLaunchKernelGGL(k_dynamics, dim3(grid1), dim3(bs), 0, st, b->P, b->dP, dFake, Kc, sampT, trigDyn, dynT, t1);
-                  hipLaunchKernelGGL(k_out_trq_sum, dim3(grid1), dim3(bs), 0, st, P, dPaths, Kc, dynT, th1, nJ + nCartRows, t1);
-               }
-            }
-         }
-         else
-         {
-            // CART path: Cartesian rows from the path splines, cable lengths from them, then the torque step
-            hipLaunchKernelGGL(k_out_eval, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, b->dPinfo, b->dSC, b->dCoef, b->dKM,
-                               sOut, segK, th0, nJ, 3, 3, t1);
-            hipLaunchKernelGGL(k_out_invkin, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, th0, t1);
-            OUT_TRY(hipGetLastError());
-            OUT_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
-            for (int k = 0; k < Kc; ++k)
-               for (int c = 0; c < 6; ++c)
-               {
-                  const size_t at = (size_t)k * 6 + c;
-                  yOff[at] = pc[k].off1 * R + (int64_t)c * pc[k].n1;
-                  sOff[at] = yOff[at];
-                  cnt[at] = pc[k].n1;
-               }
-            OUT_TRY(hipMemcpyAsync(dYOff, yOff.data(), sizeof(int64_t) * (size_t)Kc * 6, hipMemcpyHostToDevice, st));
-            OUT_TRY(hipMemcpyAsync(dSOff, sOff.data(), sizeof(int64_t) * (size_t)Kc * 6, hipMemcpyHostToDevice, st));
-            OUT_TRY(hipMemcpyAsync(dCnt, cnt.data(), sizeof(int) * (size_t)Kc * 6, hipMemcpyHostToDevice, st));
-            solveSeries(Kc * 6, dYOff, dSOff, dCnt, dRedo, th0, 1, sol1);
-            hipLaunchKernelGGL(k_out_trq, dim3((unsigned)((t1 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, th0, sol1, th1, t1);
-         }
-         if (smoothing)
-            hipLaunchKernelGGL(k_out_down, dim3((unsigned)((t2 + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, th1, th2, t2);
-         OUT_TRY(hipGetLastError());
-         if (reinterp)
-         {
-            OUT_TRY(hipStreamSynchronize(st)); // the descriptor vectors are rewritten
-            for (int k = 0; k < Kc; ++k)
-               for (int c = 0; c < R; ++c)
-               {
-                  const size_t at = (size_t)k * R + c;
-                  yOff[at] = pc[k].off2 * R + (int64_t)c * pc[k].n2;
-                  sOff[at] = yOff[at];
-                  cnt[at] = pc[k].n2;
-               }
-            OUT_TRY(hipMemcpyAsync(dYOff, yOff.data(), sizeof(int64_t) * yOff.size(), hipMemcpyHostToDevice, st));
-            OUT_TRY(hipMemcpyAsync(dSOff, sOff.data(), sizeof(int64_t) * sOff.size(), hipMemcpyHostToDevice, st));
-            OUT_TRY(hipMemcpyAsync(dCnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice, st));
-            const int series = Kc * R;
-            solveSeries(series, dYOff, dSOff, dCnt, dRedo, th2, 1, sol2);
-            hipLaunchKernelGGL(k_out_user, dim3((unsigned)((tF + bs - 1) / bs)), dim3(bs), 0, st, P, dPaths, Kc, th2, sol2, result, tF);
-            OUT_TRY(hipGetLastError());
-         }
-         if (pose)
-         {
-            // BA::q2aaVect (ba.cpp:1920-1927): quaternion rows -> axis-angle rows, the result loses the seventh Cartesian row
-            const unsigned gridF = (unsigned)((tF + bs - 1) / bs);
-            const double *atDev = nullptr;
-            if (hostTrig)
-            {
-               double *packQ = w.take<double>((size_t)tF * 2), *atTab = w.take<double>((size_t)tF);
-               if (w.at > ctx->ws[1].cap) { batotp_hip_output_destroy(o); snprintf(g_err, sizeof(g_err), "output stage: scratch estimate exceeded"); return BATOTP_ERR_STATE; }
-               hipLaunchKernelGGL(k_out_q_norm, dim3(gridF), dim3(bs), 0, st, nJ, R, dPaths, Kc, result, packQ, tF);
-               ctx->kinTheta.resize((size_t)tF * 2);
-               ctx->kinTrig.resize((size_t)tF);
-               OUT_TRY(hipMemcpyAsync(ctx->kinTheta.data(), packQ, sizeof(double) * (size_t)tF * 2, hipMemcpyDeviceToHost, st));
-               OUT_TRY(hipStreamSynchronize(st));
-               for (int k = 0; k < Kc; ++k)
-               {
-                  const int64_t off = pc[k].offF, n = pc[k].nF;
-                  for (int64_t i = 0; i < n; ++i)   // util.cpp:573: one atan2() per point, host libm
-                     ctx->kinTrig[(size_t)(off + i)] = ::atan2(ctx->kinTheta[(size_t)(off * 2 + i)], ctx->kinTheta[(size_t)(off * 2 + n + i)]);
-               }
-               OUT_TRY(hipMemcpyAsync(atTab, ctx->kinTrig.data(), sizeof(double) * (size_t)tF, hipMemcpyHostToDevice, st));
-               atDev = atTab;
-            }
-            hipLaunchKernelGGL(k_out_q2aa, dim3(gridF), dim3(bs), 0, st, nJ, R, dPaths, Kc, result, atDev, resultOut, tF);
-            OUT_TRY(hipGetLastError());
-         }
-         else if (staged)
-         {
-            hipLaunchKernelGGL(k_out_place, dim3((unsigned)((tF + bs - 1) / bs)), dim3(bs), 0, st, R, dPaths, Kc, result, resultOut, tF);
-            OUT_TRY(hipGetLastError());
-         }
-         OUT_TRY(hipStreamSynchronize(st)); // the host vectors go out of scope, the scratch is reused by the next route or chunk
+         const int ka = pl.cuts[ci], kb = pl.cuts[ci + 1];
+         OutRoute r;
+         r.L = routeLayout(pl, ka, kb, route);
+         if (r.L.t1 == 0) continue; // no path of the chunk takes this route, or every one that would failed in the sweep
+         if ((rc = poisonFill(ctx, ctx->ws[1].p, ctx->ws[1].cap, st))) return rc; // (every route starts from poisoned scratch)
+         if ((rc = carveRoute(c, route, o->dTheta + pl.all[ka].offF * c.Rout, r))) return rc;
+         if ((rc = sampleS(c, r))) return rc;
+         if ((rc = c.cable ? evalCable(c, r) : evalJoints(c, r))) return rc;
+         if ((rc = finishRoute(c, r))) return rc;
+         HIP_TRY(hipStreamSynchronize(st)); // the host vectors go out of scope, the scratch is reused by the next route or chunk
       }
-   }
-   OUT_TRY(hipEventRecord(ev1, st));
-   OUT_TRY(hipStreamSynchronize(st));
-   OUT_TRY(hipEventElapsedTime(&o->ms, ev0, ev1));
-#undef OUT_TRY
+   HIP_TRY(hipEventRecord(ev1.e, st));
+   HIP_TRY(hipStreamSynchronize(st));
+   HIP_TRY(hipEventElapsedTime(&o->ms, ev0.e, ev1.e));
    *out = o;
+   own.o = nullptr;
    return BATOTP_OK;
 }
 

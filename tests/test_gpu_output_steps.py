@@ -155,6 +155,20 @@ def test_chunked_mixed_range_equals_one_chunk(hip_lib, hip_ctx, core_expected):
     small.close(); big.close()
 
 
+def test_poisoned_scratch_and_chunk_cuts_together(hip_lib, core_expected):
+    """every route of every chunk starts from scratch filled with 0xFF bytes, and 1 MiB cuts the range into four chunks of which
+    the last mixes two routes and stages its rows (tests/test_output_plan.py checks that plan on the CPU): a launch sequence that
+    read what another chunk or route left in the workspace would now read NaNs"""
+    case, h, ys, steps = core_inputs()
+    ctx = capi.Context(hip_lib, 0)
+    ctx.set_poison(True)
+    ctx.set_workspace_budget(output_bytes=1 << 20)
+    hb = core_device_batch(ctx)
+    check_range(hb, core_expected, 1.1 * h, 5.0, what="poisoned, budget 1 MiB").close()
+    hb.close()
+    ctx.close()
+
+
 def test_the_old_contract_stands(hip_ctx, oracle_ctx, core_expected):
     case, h, ys, steps = core_inputs()
     base = core_expected.base
