@@ -171,6 +171,27 @@ class BatotpError(RuntimeError):
     pass
 
 
+# ---- audit of finished trajectories (include/batotp_hip_audit.h) -------------------------------------------------------
+AUDIT_BLOCK_POINTS = 1024   # BATOTP_AUDIT_BLOCK_POINTS: points per workgroup of the audit kernel
+AUDIT_JNT_VEL, AUDIT_JNT_ACC, AUDIT_CART_VEL, AUDIT_CART_ACC, AUDIT_TRQ = range(5)
+AUDIT_FAMILIES = ("JNT_VEL", "JNT_ACC", "CART_VEL", "CART_ACC", "TRQ")
+
+
+class AuditPeak(C.Structure):
+    """struct batotp_audit_peak"""
+    _fields_ = [("peak", C.c_double), ("at", C.c_int64), ("row", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PathAudit(C.Structure):
+    """struct batotp_path_audit"""
+    _fields_ = [("fam", AuditPeak * 5), ("n_pts", C.c_int64), ("n_over", C.c_int64), ("n_nonfinite", C.c_int64)]
+
+
+AUDIT_DTYPE = np.dtype([("fam", [("peak", "<f8"), ("at", "<i8"), ("row", "<i4"), ("reserved", "<i4")], (5,)),
+                        ("n_pts", "<i8"), ("n_over", "<i8"), ("n_nonfinite", "<i8")])
+assert AUDIT_DTYPE.itemsize == C.sizeof(PathAudit)
+
+
 def _dptr(a: Optional[np.ndarray]):
     if a is None:
         return None
@@ -271,6 +292,25 @@ class Library:
         L.batotp_hip_last_error.restype = C.c_char_p
         L.batotp_hip_last_error.argtypes = []
         self.symbols = sorted(list(sig) + ["batotp_hip_last_error"])
+        # entry points of include/batotp_hip_audit.h: bound only where the library exports them (a checker behind this class
+        # has none); `symbols` stays the table of include/batotp_hip.h
+        audit_sig = {
+            "batotp_hip_output_audit": [P, C.POINTER(Problem), C.c_double, C.c_void_p],
+            "batotp_hip_output_audit_device": [P, C.POINTER(Problem), C.c_double, C.c_void_p],
+            "batotp_hip_output_audit_ms": [P, C.POINTER(C.c_float)],
+            "batotp_hip_output_from_rows": [P, I32, C.POINTER(C.c_int64), D, I32, I32, I32, D, C.POINTER(P)],
+        }
+        self.audit_symbols = sorted(audit_sig)
+        self.has_audit = all(hasattr(L, name) for name in audit_sig)
+        if self.has_audit:
+            for name, argtypes in audit_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_audit(self):
+        if not self.has_audit:
+            raise BatotpError(f"{self.path} does not export the audit entry points (include/batotp_hip_audit.h)")
 
     def check(self, rc: int, what: str):
         if rc != 0:
@@ -480,6 +520,10 @@ class Output:
         self.n_paths, self.n_joints = n_paths, prm.n_joints
         self.handle = C.c_void_p()
         self.L.check(self.lib.batotp_hip_output(batch.handle, C.byref(prm), path0, n_paths, C.byref(self.handle)), "batotp_hip_output")
+        self._read_info()
+
+    def _read_info(self):
+        n_paths = self.n_paths
         self.n_pts = np.zeros(n_paths, dtype=np.int64)
         self.sres = np.zeros(n_paths, dtype=np.float64)
         self.L.check(self.lib.batotp_hip_output_info(self.handle, self.n_pts.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(self.sres)), "output_info")
@@ -487,6 +531,41 @@ class Output:
         self.L.check(self.lib.batotp_hip_output_channels(self.handle, C.byref(a), C.byref(b_), C.byref(c)), "output_channels")
         self.n_theta, self.n_cart, self.n_trq = a.value, b_.value, c.value
         self.n_rows = a.value + b_.value + c.value
+
+    @classmethod
+    def from_rows(cls, ctx: "Context", rows_list: Sequence[np.ndarray], sres, n_theta: int, n_cart: int, n_trq: int) -> "Output":
+        """a genuine Output from trajectories computed elsewhere (batotp_hip_output_from_rows): rows_list[k] is
+        [n_theta + n_cart + n_trq][n_pts of path k], sres[k] (or one value for all) the time step of path k"""
+        ctx.library.need_audit()
+        self = cls.__new__(cls)
+        self.lib, self.L = ctx.library.lib, ctx.library
+        self.n_paths, self.n_joints = len(rows_list), n_theta
+        R = n_theta + n_cart + n_trq
+        arrs = [np.ascontiguousarray(r, dtype=np.float64) for r in rows_list]
+        for a in arrs:
+            assert a.ndim == 2 and a.shape[0] == R, (a.shape, R)
+        n_pts = np.ascontiguousarray([a.shape[1] for a in arrs], dtype=np.int64)
+        sr = np.ascontiguousarray(np.broadcast_to(np.asarray(sres, dtype=np.float64), (len(arrs),)))
+        flat = np.ascontiguousarray(np.concatenate([a.ravel() for a in arrs])) if arrs else np.zeros(0)
+        self.handle = C.c_void_p()
+        self.L.check(self.lib.batotp_hip_output_from_rows(ctx.handle, len(arrs), n_pts.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(sr),
+                                                          n_theta, n_cart, n_trq, _dptr(flat), C.byref(self.handle)), "batotp_hip_output_from_rows")
+        self._read_info()
+        return self
+
+    def audit(self, prob: Problem, tol: float = 0.0) -> np.ndarray:
+        """the trajectories against the limits of prob, on the device (include/batotp_hip_audit.h): one AUDIT_DTYPE row per path"""
+        self.L.need_audit()
+        out = np.zeros(self.n_paths, dtype=AUDIT_DTYPE)
+        self.L.check(self.lib.batotp_hip_output_audit(self.handle, C.byref(prob), float(tol), out.ctypes.data_as(C.c_void_p)), "output_audit")
+        return out
+
+    def audit_ms(self) -> float:
+        """milliseconds of the kernels of the last audit"""
+        self.L.need_audit()
+        v = C.c_float(0)
+        self.L.check(self.lib.batotp_hip_output_audit_ms(self.handle, C.byref(v)), "output_audit_ms")
+        return float(v.value)
 
     def close(self):
         if self.handle:
@@ -524,6 +603,11 @@ class Output:
         v = C.c_float(0)
         self.L.check(self.lib.batotp_hip_output_ms(self.handle, C.byref(v)), "output_ms")
         return float(v.value)
+
+
+def output_from_rows(ctx: "Context", rows_list, sres, n_theta: int, n_cart: int, n_trq: int) -> Output:
+    """Output.from_rows"""
+    return Output.from_rows(ctx, rows_list, sres, n_theta, n_cart, n_trq)
 
 
 def sdiv_kat(ctx: "Context", a: np.ndarray, b: np.ndarray):

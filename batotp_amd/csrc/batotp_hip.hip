@@ -26,6 +26,7 @@
 #include "spline_lanes.hip.h"
 #include "resample.hip.h"
 #include "output.hip.h"
+#include "audit.hip.h"
 
 // Lanes per workgroup of a lane-per-series Thomas solve outside the hot path (resampler, output stage).  Every lane walks its own
 // stream, so a load or store instruction costs its compute unit's address path one cycle per line it touches on top of a fixed ~20
@@ -1894,3 +1895,4 @@ extern "C" int batotp_hip_batch_bytes(batotp_batch *b, int64_t *bytes)
 
 #include "resample_api.inc"
 #include "output_api.inc"
+#include "audit_api.inc"

@@ -14,6 +14,8 @@ struct batotp_output
    double *dTheta = nullptr;    // path after path, [nJ][n] each (nJ = rows per point)
    int64_t total = 0;
    float ms = 0.f;
+   float auditMs = 0.f;         // kernels of the last audit of these rows (audit_api.inc)
+   bool audited = false;
 };
 
 extern "C" int batotp_hip_output_destroy(batotp_output *o)

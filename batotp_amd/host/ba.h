@@ -130,6 +130,19 @@ struct Traj
    std::vector<Spline::splineCoeffs> cartC;
 };
 
+// Extension: what the audit of one finished trajectory found (BA::getLastAudit; the fields of batotp_path_audit,
+// include/batotp_hip_audit.h).  Families: 0 joint velocity, 1 joint acceleration, 2 Cartesian velocity, 3 Cartesian
+// acceleration, 4 torque / tension range; a family that was not audited has peak -1, at -1, row -1.
+struct BatchAudit
+{
+   double peak[5] = {-1., -1., -1., -1., -1.}; // largest utilisation of the limit (<= 1: within it)
+   long long at[5] = {-1, -1, -1, -1, -1};     // output point of the peak (time: at * sres)
+   int row[5] = {-1, -1, -1, -1, -1};          // joint / torque row of the peak, 0 for the Cartesian families
+   long long nPts = 0, nOver = 0, nNonfinite = 0;
+   double sres = 0;                            // time step of the trajectory
+   bool audited = false;                       // false: the path failed before the output stage
+};
+
 // defaults of BA::Config (reference ba.h:157-161)
 static const std::vector<double> jntVelLims_init(6, 190);
 static const std::vector<double> jntAccLims_init(6, 500);
@@ -182,6 +195,13 @@ public:
    // batotp_hip_output calls that produced the trajectories of the last optimizeBatch(): one per range of up to 1024 paths
    // where the library samples every path with its own integration step, else one per run of equal step (all devices together)
    int getLastOutputCalls() const { return _lastOutputCalls; }
+   // Extension: audit of the finished trajectories against the limits, on the device (include/batotp_hip_audit.h), while each
+   // range's trajectories are still in device memory.  tol >= 0 switches it on for the following optimizeBatch() calls
+   // (a point counts as over where a utilisation exceeds 1 + tol), a negative value off (default).  Defined in ba_audit.cpp,
+   // the only file of the library that refers to the audit entry points.
+   void setAuditTolerance(double tol);
+   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: audit off)
+   const std::vector<BatchAudit> &getLastAudit() const { return _lastAudit; }
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
    // traj.sres and the knot count in traj.nPts.  No device call.
@@ -349,6 +369,10 @@ private:
    bool _deviceOutput = true;
    double _lastOutputMs = 0, _lastOutputKernelMs = 0;
    int _lastOutputCalls = 0;
+   double _auditTol = -1;                  // setAuditTolerance
+   // audits the n paths of a batotp_output with a batotp_problem; set by setAuditTolerance (ba_audit.cpp)
+   int (*_auditFn)(void *output, const void *problem, double tol, size_t n, BatchAudit *out) = nullptr;
+   std::vector<BatchAudit> _lastAudit;
    int _deviceId = 0;
    std::vector<int> _devices;              // optimizeBatch over several GPUs (empty: _deviceId only)
    int optimizeBatchOnDevice(std::vector<Traj> &trajs);

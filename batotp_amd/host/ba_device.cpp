@@ -810,6 +810,13 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
       _lastOutputKernelMs = std::max(_lastOutputKernelMs, worker[d]._lastOutputKernelMs);
       _lastOutputCalls += worker[d]._lastOutputCalls;
    }
+   _lastAudit.clear();
+   if (_auditFn)
+   {
+      _lastAudit.assign(trajs.size(), BatchAudit());
+      for (size_t d = 0; d < nDev; ++d)
+         for (size_t q = 0; q < worker[d]._lastAudit.size() && lo[d] + q < lo[d + 1]; ++q) _lastAudit[lo[d] + q] = worker[d]._lastAudit[q];
+   }
    // what a single-device run leaves in the object (run state a later writeOutputData / interpOutputData reads)
    _isInterpolated = worker[0]._isInterpolated;
    _isParallelMech = worker[0]._isParallelMech;
@@ -922,6 +929,8 @@ int BA::deviceOutputOne(Traj &traj, const void *prmIn)
 int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
 {
    setErrorOptimization(NO_ERROR);
+   _lastAudit.clear();
+   if (_auditFn) _lastAudit.assign(trajs.size(), BatchAudit()); // (setAuditTolerance; a path that fails early keeps audited = false)
    if (trajs.empty()) return 0;
    if (_isInterpOnly || _sWeights[1] + _sWeights[2] < 1e-8)
    {
@@ -1242,6 +1251,14 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       flatAll.resize(rangePts * rows);
       rc = batotp_hip_output_download_all(og.o, flatAll.data()); // one copy for the whole range of paths
       if (rc) return fail("output_download_all", rc);
+      if (_auditFn)
+      {
+         // the trajectories of the range against the limits, while they are still in device memory
+         std::vector<BatchAudit> audit(cnt);
+         rc = _auditFn(og.o, &prob, _auditTol, cnt, audit.data());
+         if (rc) return fail("output_audit", rc);
+         for (size_t q = 0; q < cnt; ++q) _lastAudit[live[k0 + q]] = audit[q];
+      }
       size_t at = 0;
       for (size_t q = 0; q < cnt; ++q)
       {

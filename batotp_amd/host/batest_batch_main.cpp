@@ -1,7 +1,11 @@
 // batest_batch_main.cpp -- command-line driver of the many-path extension BA::optimizeBatch().
 //
-//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices]
+//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]]
 //
+// --audit [tol] (builds with -DBATOTP_HAVE_AUDIT, i.e. the product's): the finished trajectories are audited against the
+// limits on the device (BA::setAuditTolerance, include/batotp_hip_audit.h; tol defaults to 0) and one summary line names
+// the worst peak of every family with its path and time, and the paths with points over 1 + tol.  Exit status 4 if a
+// trajectory holds a value that is not finite.
 // --auto-integ-res leaves BA's class default on (reference ba.h:309; the reference's own driver switches it off,
 // test/main.cpp:53): every path then integrates with the step the rule of ba.cpp:493-556 derives from it.
 // (--host-resample / --host-output are accepted and ignored: since round 4 both stages always run behind the C-ABI.)
@@ -31,8 +35,24 @@ int main(int argc, char *argv[])
    if (nPaths < 1) return 2;
    bool hostResample = false, hostOutput = false, allDevices = false, autoIntegRes = false;
    int nDevices = 0;
+#ifdef BATOTP_HAVE_AUDIT
+   double auditTol = -1;
+#endif
    for (int k = 3; k < argc; ++k)
    {
+#ifdef BATOTP_HAVE_AUDIT
+      if (std::string(argv[k]) == "--audit")
+      {
+         auditTol = 0;
+         char *end = nullptr;
+         if (k + 1 < argc)
+         {
+            const double v = strtod(argv[k + 1], &end);
+            if (end != argv[k + 1] && *end == 0 && v >= 0) { auditTol = v; ++k; }
+         }
+         continue;
+      }
+#endif
       if (std::string(argv[k]) == "--host-resample") hostResample = true;
       if (std::string(argv[k]) == "--host-output") hostOutput = true;
       if (std::string(argv[k]) == "--all-devices") allDevices = true;
@@ -48,6 +68,9 @@ int main(int argc, char *argv[])
    planner.setDeviceResample(!hostResample);
    planner.setDeviceOutput(!hostOutput);
    if (planner.readConfigData((std::string("./") + argv[1]).c_str()) == -1) return 1;
+#ifdef BATOTP_HAVE_AUDIT
+   planner.setAuditTolerance(auditTol);
+#endif
    if (allDevices) nDevices = planner.useAllDevices();
    else if (nDevices > 0)
    {
@@ -68,6 +91,32 @@ int main(int argc, char *argv[])
           diffTime(t1, t0), "device", planner.getLastResampleMs(), "device",
           planner.getLastOutputMs(), planner.getLastOutputKernelMs());
    if (failed < 0 || failed == nPaths) return 1;
+   bool nonfinite = false;
+#ifdef BATOTP_HAVE_AUDIT
+   if (auditTol >= 0)
+   {
+      static const char *const family[5] = {"jnt_vel", "jnt_acc", "cart_vel", "cart_acc", "trq"};
+      const std::vector<BatchAudit> &audit = planner.getLastAudit();
+      printf("audit (tol %g):", auditTol);
+      for (int f = 0; f < 5; ++f)
+      {
+         int worst = -1;
+         for (size_t p = 0; p < audit.size(); ++p)
+            if (audit[p].audited && audit[p].peak[f] >= 0 && (worst < 0 || audit[p].peak[f] > audit[worst].peak[f])) worst = (int)p;
+         if (worst < 0) printf(" %s -", family[f]);
+         else printf(" %s %.6f (path %d, t %.6f s, row %d)", family[f], audit[worst].peak[f], worst, (double)audit[worst].at[f] * audit[worst].sres, audit[worst].row[f]);
+      }
+      printf("; over:");
+      int nOverPaths = 0;
+      for (size_t p = 0; p < audit.size(); ++p)
+      {
+         if (audit[p].nOver > 0) { printf(" %d(%lld)", (int)p, audit[p].nOver); ++nOverPaths; }
+         if (audit[p].nNonfinite > 0) nonfinite = true;
+      }
+      printf(nOverPaths ? "\n" : " none\n");
+      if (nonfinite) printf("audit: a trajectory holds values that are not finite\n");
+   }
+#endif
 
    const char *dirs[2] = {"./out_first/", "./out_last/"};
    const int which[2] = {0, nPaths - 1};
@@ -77,5 +126,6 @@ int main(int argc, char *argv[])
       planner.setOutputFolder(dirs[k]);
       planner.writeOutputData(paths[which[k]]);
    }
+   if (nonfinite) return 4;
    return failed == 0 ? 0 : 3;
 }
