@@ -1995,7 +1995,8 @@ __global__ void __launch_bounds__(K4_BLOCK, (G > 1 && G < 8) ? 1 : (FEAT <= 1 &&
    // BATOTP_F_CURVES_IN_PLACE (forward sweep, a.fwd == a.rev): point i of the forward curve goes to slot i, reverse point m sits in
    // slot cap - nRev + m.  The forward curve has at least as many points up to any s as the reverse curve, so slot i has been
    // left behind by the reverse-curve cursor -- checked every step with 64 points of margin (the cursor's back-steps, the
-   // prefetch and the windows of k_sweep1 stay within 32); a path that would run into live reverse points ends as if out of capacity.
+   // prefetch and the windows of k_sweep1 stay within 32; the register window of k_sweep8 / k_sweep8_lock, mvc_window.h, reads one
+   // point behind the cursor's segment and two ahead of it); a path that would run into live reverse points ends as if out of capacity.
    const int64_t revStart = (dir == 1 && a.fwd == a.rev) ? cap - (int64_t)t.nMvc : ((int64_t)1 << 62);
 #define BK_CURVE_FULL(i) ((i) >= cap || (i) + 64 >= revStart + (int64_t)t.segMVC)
 

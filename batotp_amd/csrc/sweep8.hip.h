@@ -14,13 +14,16 @@
 //   * the segment walks are wavefront-uniform loops ("while any lane moved") over select-form steps;
 //   * rare cases (a joint that stands still, a threshold test that needs its true quotient, a segment change, the end of a
 //     step) sit behind wavefront-uniform branches on ballots and cost nothing when no lane needs them;
-//   * the reverse-curve segment of the forward sweep is kept in registers and updated by ONE 16-byte load per move;
+//   * the reverse-curve segment of the forward sweep and its two neighbouring points are kept in registers (mvc_window.h): a move
+//     takes the entering point from there, and a pass of the walk in which some path moves issues two 16-byte loads in every lane,
+//     of the two neighbours of the lane's (new) segment, that nothing reads before the next such pass;
 //   * curve points leave through LDS, four at a time: one 64-byte store per path and four steps instead of four 16-byte
 //     stores (the reverse sweep's 16 384 descending streams lost their partly written lines from the L2 between the stores:
 //     3.0x the curve bytes written, profiles/r03_e).
 // Results are bit-identical to k_sweep's (every sweep test runs both; tests/test_gpu_parity.py, tests/test_gpu_fuzz.py).
 #pragma once
 #include "kernels.hip.h"
+#include "mvc_window.h"
 
 // diagnostic build (-DS8_PROFILE): what a wavefront of k_sweep8 spends its passes and cycles on, 16 doubles per wavefront in
 // SweepArgs::prof (tools/sweep8_sections.py); no effect otherwise
@@ -46,7 +49,9 @@ constexpr int S8_BLOCK = 256;
 //   kept: the certified fast-forward in both directions (profiles/r04_j_*), in the reverse sweep as a phase of its own (profiles/r06_a_*)
 //   removed: the cursor quotients through cached reciprocals, 4-7 % slower (profiles/r05_e_*, r06_a_*)
 //   removed: both next candidates beside the test in the certificate's replay, 2.3 % slower (profiles/r06_p_*)
-// (Prefetching the next point of the reverse curve in the forward sweep measured 5 % slower -- 440 against 419 ms -- and is not done.)
+//   kept: the reverse curve around the cursor in registers, its loads off the stage's dependent chain (mvc_window.h; forward launch of
+//         the headline 1655 -> 1537 ms in k_sweep8_lock, profiles/fwd_curve_window_*).  (Round 4's prefetch of the next point alone, selected
+//         into place per lane, had measured 5 % slower -- 440 against 419 ms: the select waits for the load where it stands.)
 
 // (num / den) < thr as ratio_lt (kernels.hip.h) decides it, in two parts: the product form, and whether it was decisive
 __device__ __forceinline__ bool s8_ratio_lt_fast(double num, double den, double thr, bool &decided)
@@ -356,14 +361,16 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
 #pragma unroll
    for (int q = 0; q < PER; ++q) { kEdge[q] = make_double2(0, 0); kPre[q] = make_double2(0, 0); }
    double sSeg = sres * (double)seg, sNext = sres * (double)(seg + 1); // sites of the cursor's segment
-   // reverse-curve cursor (forward sweep): segment and its two points
+   // reverse-curve cursor (forward sweep): segment, its two points and the window's two neighbours (mvc_window.h; indices clamped
+   // to the curve)
    int segM = 0;
-   double mS0 = 0, mD0 = 0, mS1 = 0, mD1 = 0;
+   double mS0 = 0, mD0 = 0, mS1 = 0, mD1 = 0, mSLo = 0, mDLo = 0, mSHi = 0, mDHi = 0;
    if (DIR == 1)
    {
       segM = t.segMVC;
-      const double2 qa = mvc[segM], qb = mvc[segM + 1];
+      const double2 qa = mvc[segM], qb = mvc[segM + 1], ql = mvc[mvc_window_lo(segM)], qh = mvc[mvc_window_hi(segM, nMvc)];
       mS0 = qa.x; mD0 = qa.y; mS1 = qb.x; mD1 = qb.y;
+      mSLo = ql.x; mDLo = ql.y; mSHi = qh.x; mDHi = qh.y;
    }
    unsigned status = t.status;
    int nfail = t.nfail;

@@ -16,7 +16,8 @@
 //     and reads all five back at the start of the next one); a failed bisection leaves w_st of the previous step as it was;
 //   * after the prologue of a stage ONE constraint check runs for all live paths; only if one of them is violated does the
 //     bisection loop run, until every path of the wavefront has ended the stage.
-// Kept as they are: the knot-cursor walk, the segment change with its prefetched knots, sweep8_mvcwalk.inc, the margin for curves in
+// Kept as they are: the knot-cursor walk, the segment change with its prefetched knots, sweep8_mvcwalk.inc (the walk of the
+// reverse-curve cursor over its register window, mvc_window.h: the one fragment both kernels include), the margin for curves in
 // place, the staging of four curve points in LDS, the certified fast-forward (s8_certify), the end snap, the short-curve tail and
 // the result row.
 // The arithmetic is a COPY of k_sweep8's with G = 8, DIR = +1 (sweep8.hip.h may not change: its code object is the validated one, and a
@@ -132,12 +133,13 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    // knot prefetch (compact pairs): knot rowSeg + 1 and the one beyond it, loaded when the cursor entered the current segment
    double2 kEdge = make_double2(0, 0), kPre = make_double2(0, 0);
    int preIdx = -(1 << 20); // knot index kPre holds (and kEdge holds preIdx - 1): none yet
-   // reverse-curve cursor: segment and its two points
+   // reverse-curve cursor: segment, its two points and the window's two neighbours (mvc_window.h; indices clamped to the curve)
    int segM = t.segMVC;
-   double mS0, mD0, mS1, mD1;
+   double mS0, mD0, mS1, mD1, mSLo, mDLo, mSHi, mDHi;
    {
-      const double2 qa = mvc[segM], qb = mvc[segM + 1];
+      const double2 qa = mvc[segM], qb = mvc[segM + 1], ql = mvc[mvc_window_lo(segM)], qh = mvc[mvc_window_hi(segM, nMvc)];
       mS0 = qa.x; mD0 = qa.y; mS1 = qb.x; mD1 = qb.y;
+      mSLo = ql.x; mDLo = ql.y; mSHi = qh.x; mDHi = qh.y;
    }
    unsigned status = t.status;
    int nfail = t.nfail;

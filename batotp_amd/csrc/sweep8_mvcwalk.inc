@@ -1,18 +1,18 @@
-// sweep8_mvcwalk.inc -- BA::updateCurSeg on the reverse curve (ba.cpp:1592, 1617-1652) inside k_sweep8 (included twice: forward
-// predictor and evalsdot).  In scope: sCur, segM, the segment's two points (mS0, mD0), (mS1, mD1), mvc, nMvc, status.  The
-// walk is the reference's comparison walk from the cached segment; a move costs one 16-byte load (the point that enters).
+// sweep8_mvcwalk.inc -- BA::updateCurSeg on the reverse curve (ba.cpp:1592, 1617-1652) inside k_sweep8 and k_sweep8_lock (included
+// twice in each: forward predictor and evalsdot).  In scope: sCur, segM, the window of four curve points around the cursor (mvc_window.h:
+// (mSLo, mDLo), the segment's (mS0, mD0), (mS1, mD1), and (mSHi, mDHi)), mvc, nMvc, status.  The walk is the reference's comparison
+// walk from the cached segment.  The point that enters the segment on a move is already in the window; a pass in which some path
+// moves issues two 16-byte loads, of the window's neighbours around the new segment, and nothing reads their result before the next
+// pass in which some path moves.  Only a second such pass of the same walk -- some path of the wavefront moves twice -- waits
+// for the loads of the first.
 {
    for (;;)
    {
-      const bool inM = (sCur >= mS0) & (sCur <= mS1);
-      const bool upM = !inM & (sCur > mS0), dnM = !inM & (sCur < mS0);
-      status |= (!inM & !upM & !dnM) ? (unsigned)BATOTP_ST_NONFINITE : 0u;
-      const bool mvUpM = upM & (segM < nMvc - 2), mvDnM = dnM & (segM > 0);
-      if (!S8_ANY(mvUpM | mvDnM)) break;
-      const double2 qM = mvc[mvUpM ? segM + 2 : (mvDnM ? segM - 1 : segM)];
-      const double nS0 = mvUpM ? mS1 : (mvDnM ? qM.x : mS0), nD0 = mvUpM ? mD1 : (mvDnM ? qM.y : mD0);
-      const double nS1 = mvUpM ? qM.x : (mvDnM ? mS0 : mS1), nD1 = mvUpM ? qM.y : (mvDnM ? mD0 : mD1);
-      mS0 = nS0; mD0 = nD0; mS1 = nS1; mD1 = nD1;
-      segM += mvUpM ? 1 : (mvDnM ? -1 : 0);
+      const MvcMove mvM = mvc_window_test(sCur, segM, nMvc, mS0, mS1);
+      status |= mvM.status;
+      if (!S8_ANY(mvM.up | mvM.dn)) break;
+      mvc_window_shift(mvM, segM, mSLo, mDLo, mS0, mD0, mS1, mD1, mSHi, mDHi);
+      const double2 qLoM = mvc[mvc_window_lo(segM)], qHiM = mvc[mvc_window_hi(segM, nMvc)];
+      mSLo = qLoM.x; mDLo = qLoM.y; mSHi = qHiM.x; mDHi = qHiM.y;
    }
 }
