@@ -84,6 +84,25 @@ class SerialModel(C.Structure):
     _fields_ = [("n_links", C.c_int32), ("degrees", C.c_int32), ("gravity", C.c_double * 3), ("link", SerialLink * 8)]
 
 
+class KinChain(C.Structure):
+    """struct batotp_kin_chain (include/batotp_hip_kin.h): joint axes, joint-origin offsets and the tool point of a serial arm"""
+    _fields_ = [("n_links", C.c_int32), ("degrees", C.c_int32), ("axis", (C.c_double * 3) * 8), ("off", (C.c_double * 3) * 8),
+                ("tool", C.c_double * 3)]
+
+
+def make_kin_chain(axis, off, tool, degrees: bool) -> KinChain:
+    """axis / off: n_links rows of 3 values, tool: 3 values"""
+    ch = KinChain()
+    ch.n_links, ch.degrees = len(axis), 1 if degrees else 0
+    assert len(off) == len(axis) <= 8
+    for i, (a, o) in enumerate(zip(axis, off)):
+        for j in range(3):
+            ch.axis[i][j], ch.off[i][j] = float(a[j]), float(o[j])
+    for j in range(3):
+        ch.tool[j] = float(tool[j])
+    return ch
+
+
 class PathResult(C.Structure):
     """struct batotp_path_result"""
 
@@ -308,6 +327,40 @@ class Library:
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
 
+        # ... and of include/batotp_hip_kin.h (the tool point of a kinematic chain), likewise
+        kin_sig = {
+            "batotp_hip_kin_chain_from_model": [C.POINTER(SerialModel), D, C.POINTER(KinChain)],
+            "batotp_hip_builtin_kin_chain": [I32, C.POINTER(KinChain)],
+            "batotp_hip_fwdkin_chain": [P, C.POINTER(KinChain), C.c_uint32, I32, C.POINTER(C.c_int64), D, D],
+            "batotp_hip_resample_chain": [P, C.POINTER(ResampleParams), C.POINTER(KinChain), I32, C.POINTER(C.c_int64), D, D, C.POINTER(P)],
+            "batotp_hip_set_kin_chain": [P, C.POINTER(KinChain)],
+        }
+        self.kin_symbols = sorted(kin_sig)
+        self.has_kin = all(hasattr(L, name) for name in kin_sig)
+        if self.has_kin:
+            for name, argtypes in kin_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_kin(self):
+        if not self.has_kin:
+            raise BatotpError(f"{self.path} does not export the kinematic-chain entry points (include/batotp_hip_kin.h)")
+
+    def builtin_kin_chain(self, robot_type: int) -> KinChain:
+        self.need_kin()
+        ch = KinChain()
+        self.check(self.lib.batotp_hip_builtin_kin_chain(robot_type, C.byref(ch)), "builtin_kin_chain")
+        return ch
+
+    def kin_chain_from_model(self, model: SerialModel, tool) -> KinChain:
+        self.need_kin()
+        ch = KinChain()
+        t = np.ascontiguousarray(tool, dtype=np.float64)
+        assert t.size == 3
+        self.check(self.lib.batotp_hip_kin_chain_from_model(C.byref(model), _dptr(t), C.byref(ch)), "kin_chain_from_model")
+        return ch
+
     def need_audit(self):
         if not self.has_audit:
             raise BatotpError(f"{self.path} does not export the audit entry points (include/batotp_hip_audit.h)")
@@ -434,8 +487,12 @@ class Resampled:
     """Uniform-s knots of a set of taught paths, produced by batotp_hip_resample and resident on the
     device (feed them to Batch.upload_knots_device)."""
 
-    def __init__(self, ctx: Context, prm: ResampleParams, x_list: Sequence[np.ndarray], sres_in: Sequence[float]):
+    def __init__(self, ctx: Context, prm: ResampleParams, x_list: Sequence[np.ndarray], sres_in: Sequence[float],
+                 chain: Optional[KinChain] = None):
+        """chain: the kinematic chain whose tool point fills the Cartesian rows of a JOINT path (batotp_hip_resample_chain)"""
         self.ctx, self.lib, self.L = ctx, ctx.library.lib, ctx.library
+        if chain is not None:
+            self.L.need_kin()
         self.n_paths = len(x_list)
         n_ch_in = prm.n_joints + prm.n_cart
         # poses (path type BOTH, 6 rows) leave the resampler as position + quaternion: one row more
@@ -446,8 +503,13 @@ class Resampled:
         flat = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(x, dtype=np.float64).ravel() for x in x_list]))
         sr = np.ascontiguousarray(sres_in, dtype=np.float64)
         self.handle = C.c_void_p()
-        self.L.check(self.lib.batotp_hip_resample(ctx.handle, C.byref(prm), self.n_paths, n_in.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                  _dptr(flat), _dptr(sr), C.byref(self.handle)), "batotp_hip_resample")
+        if chain is None:
+            self.L.check(self.lib.batotp_hip_resample(ctx.handle, C.byref(prm), self.n_paths, n_in.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      _dptr(flat), _dptr(sr), C.byref(self.handle)), "batotp_hip_resample")
+        else:
+            self.L.check(self.lib.batotp_hip_resample_chain(ctx.handle, C.byref(prm), C.byref(chain), self.n_paths,
+                                                            n_in.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(flat), _dptr(sr),
+                                                            C.byref(self.handle)), "batotp_hip_resample_chain")
         self.n_knots = np.zeros(self.n_paths, dtype=np.int64)
         self.sres = np.zeros(self.n_paths, dtype=np.float64)
         self.status = np.zeros(self.n_paths, dtype=np.uint32)
@@ -610,6 +672,25 @@ def output_from_rows(ctx: "Context", rows_list, sres, n_theta: int, n_cart: int,
     return Output.from_rows(ctx, rows_list, sres, n_theta, n_cart, n_trq)
 
 
+def fwdkin_chain(ctx: "Context", chain: KinChain, theta_list: Sequence[np.ndarray], host_trig: bool = True):
+    """tool points of a ragged set of point lists (batotp_hip_fwdkin_chain): theta_list[p] is [n_links][n_p]; returns a list of
+    [3][n_p] arrays.  host_trig: cos / sin from the host libm (bit parity with tests/kin_reference.py), else the device libm"""
+    ctx.library.need_kin()
+    arrs = [np.ascontiguousarray(t, dtype=np.float64) for t in theta_list]
+    for a in arrs:
+        assert a.ndim == 2 and a.shape[0] == chain.n_links, (a.shape, chain.n_links)
+    n_pts = np.ascontiguousarray([a.shape[1] for a in arrs], dtype=np.int64)
+    flat = np.ascontiguousarray(np.concatenate([a.ravel() for a in arrs])) if arrs else np.zeros(0)
+    out = np.empty(3 * int(n_pts.sum()), dtype=np.float64)
+    ctx.library.check(ctx.library.lib.batotp_hip_fwdkin_chain(ctx.handle, C.byref(chain), F_HOST_TRIG if host_trig else 0, len(arrs),
+                                                              n_pts.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(flat), _dptr(out)), "fwdkin_chain")
+    res, at = [], 0
+    for n in n_pts:
+        res.append(out[at: at + 3 * int(n)].reshape(3, int(n)))
+        at += 3 * int(n)
+    return res
+
+
 def sdiv_kat(ctx: "Context", a: np.ndarray, b: np.ndarray):
     """(a / b as k_sweep8 divides by a shared reciprocal, which operand pairs went through the reciprocal)"""
     a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
@@ -694,6 +775,11 @@ class Batch:
 
     def set_serial_model(self, model: SerialModel):
         self.L.check(self.lib.batotp_hip_set_serial_model(self.handle, C.byref(model)), "set_serial_model")
+
+    def set_kin_chain(self, chain: KinChain):
+        """the kinematic chain whose tool point the output stage puts into the three Cartesian rows of a JOINT path"""
+        self.L.need_kin()
+        self.L.check(self.lib.batotp_hip_set_kin_chain(self.handle, C.byref(chain)), "set_kin_chain")
 
     def upload_joint_trig(self, path: int, trig: np.ndarray):
         """trig: [2*n_joints][N] cosines, then sines, of the joint angles (radians) at the knot samples"""

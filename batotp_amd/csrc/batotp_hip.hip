@@ -27,6 +27,7 @@
 #include "resample.hip.h"
 #include "output.hip.h"
 #include "audit.hip.h"
+#include "kin_chain.hip.h"
 
 // Lanes per workgroup of a lane-per-series Thomas solve outside the hot path (resampler, output stage).  Every lane walks its own
 // stream, so a load or store instruction costs its compute unit's address path one cycle per line it touches on top of a fixed ~20
@@ -188,6 +189,8 @@ struct batotp_batch
    batotp_serial_model hModel;            // ... its host copy (the output stage needs `degrees` for its trig tables)
    double *dJTrig = nullptr; // [2*nJ][N] per path: host cosines / sines of the joint angles for the serial-chain dynamics
    bool hasSerial = false, jtrigSet = false;
+   batotp_kin_chain kinChain;             // kinematic chain of the output stage's tool point (batotp_hip_set_kin_chain)
+   bool hasKinChain = false;
    // K1 in tiles (spline_tile.hip.h): tiles per path (prefix sums), boundary values between tiles, series left to the
    // sequential kernel (short paths from the start; a series whose boundary comparison failed)
    int *dTileOff = nullptr, *dDirty = nullptr;
@@ -1896,3 +1899,4 @@ extern "C" int batotp_hip_batch_bytes(batotp_batch *b, int64_t *bytes)
 #include "resample_api.inc"
 #include "output_api.inc"
 #include "audit_api.inc"
+#include "kin_api.inc"

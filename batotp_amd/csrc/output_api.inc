@@ -75,7 +75,7 @@ struct OutCall
    batotp_batch *b;
    batotp_ctx *ctx;
    hipStream_t st;
-   bool cable, kin, serialTrq, both, pose, hostTrig;
+   bool cable, kin, chainKin, serialTrq, both, pose, hostTrig;   // chainKin: kin by the batch's kinematic chain, not a closed form
    int trigRows, nJ, nCartRows, nTrqRows;
    int R;    // rows per point the stage works with: joints (+ Cartesian + torques)
    int Rout; // rows per point of the result (poses leave as position + axis-angle)
@@ -118,7 +118,9 @@ static int outputCall(batotp_batch *b, const batotp_output_params *prm, int32_t 
                       b->prob.n_cart == 3 && (b->prob.flags & BATOTP_F_TRQ_ON) && (b->prob.flags & BATOTP_F_PARALLEL);
    const bool jointPath = prm->path_type == BATOTP_PATH_JOINT || prm->path_type == 0;
    // JOINT path of a robot with forward kinematics (KUKA, RR; SURVEY.md 8 f-3): three Cartesian rows from the joint rows
-   const int trigRows = fwdkin_trig_rows(b->prob.robot_type, prm->n_joints);
+   // ... or of any robot whose batch has a kinematic chain (batotp_hip_set_kin_chain): the chain's tool point, tables of kind 2
+   const bool chainKin = jointPath && b->hasKinChain;
+   const int trigRows = chainKin ? 2 * prm->n_joints : fwdkin_trig_rows(b->prob.robot_type, prm->n_joints);
    const bool kin = jointPath && trigRows != 0 && b->prob.n_cart >= 3;
    // torque recomputation of a serial robot (ba.cpp:1791-1827): the two-link arm's closed form or the batch's chain model
    const bool serialTrq = jointPath && (b->prob.flags & BATOTP_F_TRQ_ON) && !(b->prob.flags & BATOTP_F_PARALLEL) &&
@@ -129,7 +131,7 @@ static int outputCall(batotp_batch *b, const batotp_output_params *prm, int32_t 
    const bool both = prm->path_type == BATOTP_PATH_BOTH && b->prob.n_cart >= 3 && b->prob.n_cart <= BATOTP_MAX_CART && !(b->prob.flags & BATOTP_F_TRQ_ON);
    const bool pose = both && b->prob.n_cart == 7;
    if ((!cable && !jointMode && !both) || prm->n_joints != b->P.nJ || !(prm->out_res > 0) || !(prm->integ_res > 0 || prm->integ_res == BATOTP_OUT_STEP_PER_PATH) || !(prm->out_smooth_fact >= 1) ||
-       (kin && b->prob.robot_type == BATOTP_ROBOT_RR && (b->prob.flags & BATOTP_F_NO_SAMPLES)))
+       (kin && !chainKin && b->prob.robot_type == BATOTP_ROBOT_RR && (b->prob.flags & BATOTP_F_NO_SAMPLES)))
    {
       snprintf(g_err, sizeof(g_err), "output stage: configuration not supported on the device");
       return BATOTP_ERR_ARG;
@@ -151,7 +153,7 @@ static int outputCall(batotp_batch *b, const batotp_output_params *prm, int32_t 
    if (rc) return rc;
    const int nJ = b->P.nJ;
    c.b = b; c.ctx = b->ctx; c.st = b->ctx->stream;
-   c.cable = cable; c.kin = kin; c.serialTrq = serialTrq; c.both = both; c.pose = pose;
+   c.cable = cable; c.kin = kin; c.chainKin = kin && chainKin; c.serialTrq = serialTrq; c.both = both; c.pose = pose;
    c.hostTrig = (b->prob.flags & BATOTP_F_HOST_TRIG) != 0;
    c.trigRows = trigRows; c.nJ = nJ;
    c.nCartRows = cable ? 3 : (both ? (int)b->prob.n_cart : (kin ? 3 : 0));
@@ -346,10 +348,14 @@ static int evalJoints(const OutCall &c, OutRoute &r)
       if (c.hostTrig)
       {
          hipLaunchKernelGGL(k_out_pack_theta, grid256(t1), dim3(OUT_BS), 0, st, c.P, r.dPaths, Kc, thA, kn.pack, t1);
-         if ((rc = tableFor(c, r, kn, 0, 1.0))) return rc;
+         if ((rc = tableFor(c, r, kn, c.chainKin ? 2 : 0, (c.chainKin && b->kinChain.degrees) ? KIN_DEG2RAD : 1.0))) return rc;
       }
-      hipLaunchKernelGGL(k_out_fwdkin, grid256(t1), dim3(OUT_BS), 0, st, c.P, b->prob.robot_type, r.dPaths, Kc, thA,
-                         c.hostTrig ? kn.trig : (const double *)nullptr, c.trigRows, b->dPinfo, b->dSamp, t1);
+      if (c.chainKin)
+         hipLaunchKernelGGL(k_out_fwdkin_chain, grid256(t1), dim3(OUT_BS), 0, st, c.P, b->kinChain, r.dPaths, Kc, thA,
+                            c.hostTrig ? kn.trig : (const double *)nullptr, t1);
+      else
+         hipLaunchKernelGGL(k_out_fwdkin, grid256(t1), dim3(OUT_BS), 0, st, c.P, b->prob.robot_type, r.dPaths, Kc, thA,
+                            c.hostTrig ? kn.trig : (const double *)nullptr, c.trigRows, b->dPinfo, b->dSamp, t1);
    }
    return c.serialTrq ? serialTorque(c, r, kn) : BATOTP_OK;
 }

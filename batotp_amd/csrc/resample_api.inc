@@ -208,11 +208,13 @@ void hostTrigTables(int kind, int robot, int nJ, double unit, const std::vector<
 }
 
 // Robot::fwdKin on a stage (x: [C][n] per path): Cartesian rows from the joint rows.  paths = host copy of dPaths with the
-// current point counts.
-int rsFwdKin(batotp_ctx *ctx, const RsParams &P, bool hostTrig, const std::vector<RsPath> &paths, const RsPath *dPaths, double *x, int64_t total)
+// current point counts.  chain != nullptr: the tool point of that kinematic chain (kin_chain.hip.h) instead of the robot type's
+// closed form, its host tables those of the chain model (kind 2).
+int rsFwdKin(batotp_ctx *ctx, const RsParams &P, const batotp_kin_chain *chain, bool hostTrig, const std::vector<RsPath> &paths, const RsPath *dPaths, double *x,
+             int64_t total)
 {
    hipStream_t st = ctx->stream;
-   const int B = (int)paths.size(), bs = 256, rows = fwdkin_trig_rows(P.robot, P.nJ);
+   const int B = (int)paths.size(), bs = 256, rows = chain ? 2 * P.nJ : fwdkin_trig_rows(P.robot, P.nJ);
    const unsigned grid = (unsigned)((total + bs - 1) / bs);
    const double *trigDev = nullptr;
    if (hostTrig)
@@ -229,11 +231,12 @@ int rsFwdKin(batotp_ctx *ctx, const RsParams &P, bool hostTrig, const std::vecto
       HIP_TRY(hipStreamSynchronize(st));
       std::vector<TrigSpan> spans(paths.size());
       for (size_t p = 0; p < paths.size(); ++p) spans[p] = TrigSpan{paths[p].off, paths[p].n, paths[p].status != 0};
-      hostTrigTables(0, P.robot, P.nJ, 1.0, spans, ctx->kinTheta.data(), ctx->kinTrig.data());
+      hostTrigTables(chain ? 2 : 0, P.robot, P.nJ, (chain && chain->degrees) ? KIN_DEG2RAD : 1.0, spans, ctx->kinTheta.data(), ctx->kinTrig.data());
       HIP_TRY(hipMemcpyAsync(trig, ctx->kinTrig.data(), sizeof(double) * ctx->kinTrig.size(), hipMemcpyHostToDevice, st));
       trigDev = trig;
    }
-   RS_LAUNCH(st, k_rs_fwdkin, dim3(grid), dim3(bs), P, dPaths, B, x, trigDev, rows, total);
+   if (chain) RS_LAUNCH(st, k_rs_fwdkin_chain, dim3(grid), dim3(bs), P, *chain, dPaths, B, x, trigDev, total);
+   else RS_LAUNCH(st, k_rs_fwdkin, dim3(grid), dim3(bs), P, dPaths, B, x, trigDev, rows, total);
    HIP_TRY(hipGetLastError());
    if (hostTrig) HIP_TRY(hipStreamSynchronize(st)); // the host table may be rewritten by the next call
    return BATOTP_OK;
@@ -273,7 +276,8 @@ size_t chunkBytesOfPath(const RsPath &q, int C)
 
 // stages 0b..2 for the paths of p0 (offsets local to x0 / s0); the knots are appended to the
 // context's knot workspace at *yUsed (doubles); fills n2 / sres / status
-int rsChunk(batotp_ctx *ctx, RsParams P, const batotp_resample_params *prm, bool cable, bool kin, bool hostTrig, std::vector<RsPath> &p0, const double *x0,
+int rsChunk(batotp_ctx *ctx, RsParams P, const batotp_resample_params *prm, const batotp_kin_chain *chain, bool cable, bool kin, bool hostTrig,
+            std::vector<RsPath> &p0, const double *x0,
             const double *s0, int64_t *yUsed, int64_t *n2, double *sresOut, uint32_t *statusOut, double *autoOut)
 {
    hipStream_t st = ctx->stream;
@@ -347,7 +351,7 @@ int rsChunk(batotp_ctx *ctx, RsParams P, const batotp_resample_params *prm, bool
    HIP_TRY(hipMemcpyAsync(dP1, p1.data(), sizeof(RsPath) * B, hipMemcpyHostToDevice, st));
    RS_LAUNCH(st, k_rs_transpose, dim3((unsigned)((tot1 + bs - 1) / bs)), dim3(bs), C, dP0, dP1, B, rows, x1, tot1);
    if (cable) RS_LAUNCH(st, k_rs_invkin_cspr, dim3((unsigned)((tot1 + bs - 1) / bs)), dim3(bs), P, dP1, B, x1, tot1);
-   if (kin && (rc = rsFwdKin(ctx, P, hostTrig, p1, dP1, x1, tot1))) return rc; // ba.cpp:626-628
+   if (kin && (rc = rsFwdKin(ctx, P, chain, hostTrig, p1, dP1, x1, tot1))) return rc; // ba.cpp:626-628
    P.thetaRes = prm->theta_norm_res2; P.cartRes = prm->cart_norm_res2;
    if ((rc = rsArcLengths(st, P, dP1, B, x1, ta1, ca1, s1, tot1, 0))) return rc;
    HIP_TRY(hipMemcpyAsync(p1.data(), dP1, sizeof(RsPath) * B, hipMemcpyDeviceToHost, st));
@@ -387,7 +391,7 @@ int rsChunk(batotp_ctx *ctx, RsParams P, const batotp_resample_params *prm, bool
    if ((rc = rsSplines(ctx, p1, C, x1, sol1, dPinfo, dRedo))) return rc;
    RS_LAUNCH(st, k_rs_regular, dim3((unsigned)((tot2 + bs - 1) / bs)), dim3(bs), P, dP1, dP2, B, s1, x1, sol1, y, tot2);
    if (cable) RS_LAUNCH(st, k_rs_invkin_cspr, dim3((unsigned)((tot2 + bs - 1) / bs)), dim3(bs), P, dP2, B, y, tot2);
-   if (kin && (rc = rsFwdKin(ctx, P, hostTrig, p2, dP2, y, tot2))) return rc; // ba.cpp:626-628
+   if (kin && (rc = rsFwdKin(ctx, P, chain, hostTrig, p2, dP2, y, tot2))) return rc; // ba.cpp:626-628
    HIP_TRY(hipGetLastError());
    HIP_TRY(hipStreamSynchronize(st));
    if (trace && !p1[0].status && ((rc = rsTraceSum(ctx, 6, sol1, (int64_t)p1[0].n * C)) || (rc = rsTraceSum(ctx, 7, y, tot2 * C)))) return rc;   // stage 1's second derivatives, the knots
@@ -401,8 +405,9 @@ extern "C" int batotp_hip_resampled_destroy(batotp_resampled *r)
    return BATOTP_OK;
 }
 
-extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params *prm, int32_t n_paths, const int64_t *n_in, const double *x,
-                                   const double *sres_in, batotp_resampled **out)
+// batotp_hip_resample and batotp_hip_resample_chain (kin_api.inc, which has checked the chain): chain == nullptr is the former
+static int resampleRun(batotp_ctx *ctx, const batotp_resample_params *prm, const batotp_kin_chain *chain, int32_t n_paths, const int64_t *n_in, const double *x,
+                       const double *sres_in, batotp_resampled **out)
 {
    if (!ctx || !prm || !n_in || !x || !sres_in || !out || n_paths < 1) return BATOTP_ERR_ARG;
    *out = nullptr;
@@ -414,10 +419,11 @@ extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params
    const int nJ = prm->n_joints, nCin = prm->n_cart, nC = nCin + (pose ? 1 : 0), C = nJ + nC, B = n_paths;
    if (nJ < 1 || nJ > BATOTP_MAX_JOINTS || nC < 3 || nC > BATOTP_MAX_CART) return BATOTP_ERR_ARG;
    if (nJ > 8 || nC > 8) { snprintf(g_err, sizeof(g_err), "resample: the walk kernel carries at most 8 joints and 8 Cartesian channels"); return BATOTP_ERR_ARG; }
-   const bool joint = prm->path_type == BATOTP_PATH_JOINT && prm->robot_type == BATOTP_ROBOT_GENJNT;
+   // (with a chain the Cartesian rows of the caller are not read either: zero until the chain's tool point replaces them)
+   const bool joint = prm->path_type == BATOTP_PATH_JOINT && (prm->robot_type == BATOTP_ROBOT_GENJNT || chain);
    const bool cable = prm->path_type == BATOTP_PATH_CART && prm->robot_type == BATOTP_ROBOT_CSPR3DOF && nJ == 3;
-   // JOINT paths of the robots with forward kinematics (KUKA, RR; SURVEY.md 8 f-3)
-   const bool kin = prm->path_type == BATOTP_PATH_JOINT && fwdkin_trig_rows(prm->robot_type, nJ) != 0;
+   // JOINT paths of the robots with forward kinematics (KUKA, RR; SURVEY.md 8 f-3), or of any robot with a kinematic chain
+   const bool kin = prm->path_type == BATOTP_PATH_JOINT && (chain || fwdkin_trig_rows(prm->robot_type, nJ) != 0);
    const bool hostTrig = (kin || pose) && (prm->flags & BATOTP_F_HOST_TRIG) != 0;
    const bool cartOn = (prm->flags & (BATOTP_F_CART_VEL_ON | BATOTP_F_CART_ACC_ON)) != 0;
    if (!joint && !cable && !kin && !both) { snprintf(g_err, sizeof(g_err), "resample: path/robot kind not supported on the device"); return BATOTP_ERR_ARG; }
@@ -595,7 +601,7 @@ extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpyAsync(p0.data(), dP0, sizeof(RsPath) * B, hipMemcpyDeviceToHost, st)); // point counts after remClosePts
       HIP_TRY(hipStreamSynchronize(st));
-      if ((rc = rsFwdKin(ctx, P, hostTrig, p0, dP0, x0, tot0))) return rc;
+      if ((rc = rsFwdKin(ctx, P, chain, hostTrig, p0, dP0, x0, tot0))) return rc;
    }
    P.thetaRes = prm->theta_norm_res; P.cartRes = prm->cart_norm_res;
    if ((rc = rsArcLengths(st, P, dP0, B, x0, ta0, ca0, s0, tot0, 1))) return rc;
@@ -642,7 +648,7 @@ extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params
       std::vector<RsPath> pc(p0.begin() + pa, p0.begin() + pb);
       const int64_t base = p0[pa].off;
       for (RsPath &q : pc) q.off -= base;
-      rc = rsChunk(ctx, P, prm, cable, kin, hostTrig, pc, x0 + base * C, s0 + base, &yUsed, r->n.data() + pa, r->sres.data() + pa, r->status.data() + pa,
+      rc = rsChunk(ctx, P, prm, chain, cable, kin, hostTrig, pc, x0 + base * C, s0 + base, &yUsed, r->n.data() + pa, r->sres.data() + pa, r->status.data() + pa,
                    r->au.data() + 5 * (size_t)pa);
       if (rc) { delete r; return rc; }
    }
@@ -660,6 +666,12 @@ extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params
    if (e != hipSuccess) { delete r; return hipFail(e, "resample timing"); }
    *out = r;
    return BATOTP_OK;
+}
+
+extern "C" int batotp_hip_resample(batotp_ctx *ctx, const batotp_resample_params *prm, int32_t n_paths, const int64_t *n_in, const double *x,
+                                   const double *sres_in, batotp_resampled **out)
+{
+   return resampleRun(ctx, prm, nullptr, n_paths, n_in, x, sres_in, out);
 }
 
 static int rsLive(batotp_resampled *r)

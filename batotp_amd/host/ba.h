@@ -225,6 +225,13 @@ public:
    // include/batotp_hip.h (link table of a chain of revolute joints).  Robot type KUKA has a built-in table
    // (include/batotp_models.h: LWR IV+, nominal inertial parameters) that is used when none is set.
    void setSerialModel(const void *batotp_serial_model_in);
+   // Extension: Cartesian limits on a joint path of an arm without closed-form kinematics (robot types UR and GENJNT; the
+   // reference knows the tool point of KUKA and RR only, robot.cpp:73-96).  With a chain model set (setSerialModel: axes and
+   // joint-origin offsets) and the tool point relative to its last joint origin, JOINT paths with three Cartesian channels
+   // of those robot types are resampled and put out with the tool point of the chain (include/batotp_hip_kin.h),
+   // Cartesian limits on or off.  Defined in ba_kin.cpp, the only file of the library that refers to the entry points of
+   // that header.
+   void setToolPoint(const double tool[3]);
    unsigned int getNumJoints() const { return _nJoints; }
    unsigned int getNumCart() const { return _nCart; }
 
@@ -373,6 +380,13 @@ private:
    // audits the n paths of a batotp_output with a batotp_problem; set by setAuditTolerance (ba_audit.cpp)
    int (*_auditFn)(void *output, const void *problem, double tol, size_t n, BatchAudit *out) = nullptr;
    std::vector<BatchAudit> _lastAudit;
+   // batotp_hip_resample_chain / batotp_hip_set_kin_chain behind pointers; set by setToolPoint (ba_kin.cpp)
+   int (*_kinResampleFn)(void *ctx, const void *params, const void *chain, int nPaths, const int64_t *nIn, const double *x, const double *sresIn,
+                         void **out) = nullptr;
+   int (*_kinBatchFn)(void *batch, const void *chain) = nullptr;
+   bool chainKinematics(void *batotp_kin_chain_out) const; // does this configuration take its tool point from a chain?
+   int resampleCall(const void *params, int nPaths, const int64_t *nIn, const double *x, const double *sresIn, void **out); // with or without it
+   int deviceKinChain(void *batch);        // hand the chain, if the configuration uses one, to a batch before its output stage
    int _deviceId = 0;
    std::vector<int> _devices;              // optimizeBatch over several GPUs (empty: _deviceId only)
    int optimizeBatchOnDevice(std::vector<Traj> &trajs);

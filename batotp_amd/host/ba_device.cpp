@@ -118,7 +118,8 @@ void BA::fillProblem(void *out) const
    // cos/sin from the host libm: bit parity with the reference (RR), and with the host twin of the chain model
    // ... and with the forward kinematics of the device resampler / output stage (KUKA, RR)
    //     and with the pose conversions of a BOTH path (atan2 of the output stage)
-   if (_robotType == RR || _robotType == KUKA || _pathType == BOTH || (_isTrqConOn && !_isParallelMechOrig)) f |= BATOTP_F_HOST_TRIG;
+   //     and with the host twin of the kinematic chain's tool point (UR / GENJNT after BA::setToolPoint)
+   if (_robotType == RR || _robotType == KUKA || _pathType == BOTH || (_isTrqConOn && !_isParallelMechOrig) || chainKinematics(nullptr)) f |= BATOTP_F_HOST_TRIG;
    P.flags = f;
    for (unsigned int j = 0; j < _nJoints && j < BATOTP_MAX_JOINTS; ++j)
    {
@@ -182,6 +183,36 @@ int BA::deviceSerialDynamicsInputs(void *batch, int pathIndex, const double *con
    return 0;
 }
 
+// JOINT paths of an arm without closed-form kinematics (UR, GENJNT) take their tool point from a kinematic chain once the
+// caller has set a chain model and a tool point (BA::setToolPoint, ba_kin.cpp); *out (may be null) receives the chain
+bool BA::chainKinematics(void *out) const
+{
+   if (!_kinResampleFn || !_kinBatchFn || _pathType != JOINT || _nCart != 3 || !(_robotType == GENJNT || _robotType == UR)) return false;
+   batotp_kin_chain ch;
+   if (!const_cast<Robot &>(myRobot).kinChain(&ch) || ch.n_links != (int32_t)_nJoints) return false;
+   if (out) *static_cast<batotp_kin_chain *>(out) = ch;
+   return true;
+}
+
+// batotp_hip_resample, or its form with the chain as the kinematics
+int BA::resampleCall(const void *params, int nPaths, const int64_t *nIn, const double *x, const double *sresIn, void **out)
+{
+   batotp_kin_chain ch;
+   if (chainKinematics(&ch)) return _kinResampleFn(_gpu->ctx, params, &ch, nPaths, nIn, x, sresIn, out);
+   batotp_resampled *r = nullptr;
+   const int rc = batotp_hip_resample(_gpu->ctx, static_cast<const batotp_resample_params *>(params), (int32_t)nPaths, nIn, x, sresIn, &r);
+   *out = r;
+   return rc;
+}
+
+int BA::deviceKinChain(void *batch)
+{
+   batotp_kin_chain ch;
+   if (!chainKinematics(&ch)) return 0;
+   const int rc = _kinBatchFn(batch, &ch);
+   return rc ? fail("set_kin_chain", rc) : 0;
+}
+
 // Which configurations batotp_hip_resample covers (what it does not, interpInputData refuses with a message).
 int BA::exportResampleParams(const Traj &traj, void *out) const
 {
@@ -235,8 +266,11 @@ int BA::exportResampleParams(const Traj &traj, void *out) const
    // Cartesian rows are tool poses (the UR5 example): orientations as axis-angle -> quaternions (BA::aa2qVect, ba.cpp:327-369; sine /
    // cosine of the half angle from the host libm); any other count (tool positions without orientations) goes through unchanged
    const bool both = _pathType == BOTH;
-   if (kin || (both && _nCart == 6)) R.flags |= BATOTP_F_HOST_TRIG;
-   return (joint || cable || kin || both) ? 0 : -1;
+   // ... and of UR / GENJNT with a kinematic chain (BA::setToolPoint), Cartesian limits on or off: the same, with the chain's
+   // tool point (batotp_hip_resample_chain)
+   const bool chain = chainKinematics(nullptr);
+   if (kin || chain || (both && _nCart == 6)) R.flags |= BATOTP_F_HOST_TRIG;
+   return (joint || cable || kin || chain || both) ? 0 : -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -290,7 +324,9 @@ int BA::deviceResampleOne(Traj &traj)
    for (int pass = 0; pass < 4 && !agreed; ++pass)
    {
       ResampledGuard rs;
-      int rc = batotp_hip_resample(_gpu->ctx, &rsp, 1, &n, x.data(), &sresIn, &rs.r);
+      void *handle = nullptr;
+      int rc = resampleCall(&rsp, 1, &n, x.data(), &sresIn, &handle);
+      rs.r = static_cast<batotp_resampled *>(handle);
       if (rc) return fail("resample", rc);
       const bool traced = batotp_hip_resampled_trace(rs.r, traceAgain) == BATOTP_OK;
       std::vector<double> stageAgain[2];   // stages 2 and 3 of this evaluation (a few MB)
@@ -428,7 +464,9 @@ int BA::exportOutputParams(void *out) const
    // ba.cpp:1722-1725) and, with torque constraints, the serial-robot torque recomputation (ba.cpp:1791-1827) with the
    // two-link arm's closed form or the chain model
    const bool kinRobot = _pathType == JOINT && _nCart == 3 && ((_robotType == KUKA && _nJoints == 7) || (_robotType == RR && _nJoints == 2));
-   const bool kin = kinRobot && (!_isTrqConOn || (!_isParallelMechOrig && (_robotType == RR || const_cast<Robot &>(myRobot).serialModel() != nullptr)));
+   // (UR / GENJNT with a kinematic chain, BA::setToolPoint: the chain's tool point; its model serves the torques)
+   const bool kin = (kinRobot || chainKinematics(nullptr)) &&
+                    (!_isTrqConOn || (!_isParallelMechOrig && (_robotType == RR || const_cast<Robot &>(myRobot).serialModel() != nullptr)));
    // joints and Cartesian rows together (ba.cpp:1726-1736: the Cartesian rows are evaluated like the joints); pose rows are quaternions
    // during the run (_nCart == 7) and leave as axis-angle (BA::q2aaVect, ba.cpp:384-403)
    const bool both = _pathType == BOTH && _nCart >= 3 && _nCart <= BATOTP_MAX_CART && !_isTrqConOn;
@@ -895,6 +933,7 @@ int BA::deviceOutputOne(Traj &traj, const void *prmIn)
       rc = batotp_hip_set_serial_model(g.b, myRobot.serialModel());
       if (rc) return fail("set_serial_model", rc);
    }
+   if (prob.n_cart >= 3 && deviceKinChain(g.b) != 0) return -1;
    if (nF == 4 && traj.tMVC.size() == 4 && traj.tMVC[1] != _integRes)
    {
       // the four-point fix-up of a curve of fewer than four integration steps (ba.cpp:1171-1184) spaces its points by T/3:
@@ -998,7 +1037,9 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          std::vector<uint32_t> stP(trajs.size());
          std::vector<uint64_t> sumsP(trajs.size());
          if (rs.r) { batotp_hip_resampled_destroy(rs.r); rs.r = nullptr; }
-         rcR = batotp_hip_resample(_gpu->ctx, &rsp, (int32_t)trajs.size(), nTaught.data(), x.data(), sresTaught.data(), &rs.r);
+         void *handle = nullptr;
+         rcR = resampleCall(&rsp, (int)trajs.size(), nTaught.data(), x.data(), sresTaught.data(), &handle);
+         rs.r = static_cast<batotp_resampled *>(handle);
          if (rcR) return fail("resample", rcR);
          rcR = batotp_hip_resampled_info(rs.r, nP.data(), srP.data(), stP.data());
          if (rcR) return fail("resampled_info", rcR);
@@ -1097,6 +1138,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       if (2 * cap >= 3 * nMax) prob.flags |= BATOTP_F_MVC_IN_CURVES; else prob.flags &= ~(uint32_t)BATOTP_F_MVC_IN_CURVES;
       rc = batotp_hip_batch_create(_gpu->ctx, &prob, (int32_t)live.size(), nKnots.data(), cap, &g.b);
       if (rc) return fail("batch_create", rc);
+      if (deviceKinChain(g.b) != 0) return -1; // (the output stage's tool point, where the configuration has a chain)
       if (_isAutoIntegRes)
       {
          rc = batotp_hip_set_path_integ_res(g.b, 0, (int32_t)live.size(), integOf.data());

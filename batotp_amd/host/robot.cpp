@@ -84,8 +84,71 @@ int Robot::call_fwdKin(const Channels &theta, Channels &cart)
 {
    if (_kind == KUKA) { kukaToolPoint(theta, cart); return 0; }
    if (_kind == RR) { planarRRToolPoint(theta, cart); return 0; }
+   // no closed form: the chain of the serial model, once a tool point is set (include/batotp_hip_kin.h)
+   if (_hasTool && serialModel() != nullptr) return chainToolPoint(theta, cart);
    printf("No forward Kinematics model provided for robotType=%s.\n", _kindName.c_str());
    return -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// tool point of a kinematic chain (include/batotp_hip_kin.h: the definition, word for word; this project's own)
+// ---------------------------------------------------------------------------------------------
+namespace
+{
+// two separate libm calls: side by side and inlined, the optimiser would make one sincos() of them (see kinSinCos above)
+double __attribute__((noinline)) plainSin(double x) { return std::sin(x); }
+} // namespace
+
+void Robot::setToolPoint(const double tool[3])
+{
+   for (int j = 0; j < 3; ++j) _tool[j] = tool[j];
+   _hasTool = true;
+}
+
+bool Robot::kinChain(batotp_kin_chain *out)
+{
+   const batotp_serial_model *m = serialModel();
+   if (!m || !_hasTool || m->n_links < 1 || m->n_links > BATOTP_MAX_LINKS) return false;
+   batotp_kin_chain_of_model(m, _tool, out);
+   return true;
+}
+
+int Robot::chainToolPoint(const Channels &theta, Channels &cart)
+{
+   batotp_kin_chain ch;
+   if (!kinChain(&ch))
+   {
+      printf("No kinematic chain (serial model and tool point) provided for robotType=%s.\n", _kindName.c_str());
+      return -1;
+   }
+   if ((size_t)ch.n_links != theta.size())
+   {
+      printf("Kinematic chain has %d links but the path has %d joints.\n", (int)ch.n_links, (int)theta.size());
+      return -1;
+   }
+   const int n = (int)theta[0].size();
+   const double unit = ch.degrees ? _DEG2RAD : 1.0;
+   cart.resize(3);
+   for (int k = 0; k < 3; ++k) cart[k].resize(n);
+   for (int i = 0; i < n; ++i)
+   {
+      double p0 = ch.tool[0], p1 = ch.tool[1], p2 = ch.tool[2];
+      for (int l = ch.n_links - 1; l >= 0; --l)
+      {
+         const double q = unit * theta[l][i];
+         const double c = plainCos(q), s = plainSin(q);
+         const double a0 = ch.axis[l][0], a1 = ch.axis[l][1], a2 = ch.axis[l][2];
+         const double d = (a0 * p0 + a1 * p1) + a2 * p2;
+         const double x0 = a1 * p2 - a2 * p1, x1 = a2 * p0 - a0 * p2, x2 = a0 * p1 - a1 * p0;
+         const double k = d * (1.0 - c);
+         const double n0 = ch.off[l][0] + ((p0 * c + x0 * s) + a0 * k);
+         const double n1 = ch.off[l][1] + ((p1 * c + x1 * s) + a1 * k);
+         const double n2 = ch.off[l][2] + ((p2 * c + x2 * s) + a2 * k);
+         p0 = n0; p1 = n1; p2 = n2;
+      }
+      cart[0][i] = p0; cart[1][i] = p1; cart[2][i] = p2;
+   }
+   return 0;
 }
 
 // KUKA LWR IV+ tool point (reference robot.cpp:105-174)

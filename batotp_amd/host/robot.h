@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "batotp_hip.h" // POD batotp_serial_model only
+#include "batotp_hip_kin.h" // POD batotp_kin_chain only
 
 namespace BATOTP
 {
@@ -49,6 +50,14 @@ public:
    // (include/batotp_models.h: KUKA LWR IV+).  serialModel() returns nullptr when there is neither.
    void setSerialModel(const batotp_serial_model &m) { _serial = m; _hasSerial = true; }
    const batotp_serial_model *serialModel();
+   // extension: the tool point of a robot without closed-form kinematics (UR, GENJNT), from the chain of the serial model
+   // set with setSerialModel() and a tool point relative to its last joint origin (include/batotp_hip_kin.h has the
+   // definition; chainToolPoint is its host twin, cos / sin as two separate libm calls).  call_fwdKin() uses it for such a
+   // robot once both are set.  kinChain() fills the POD the device layer takes; false without a model or a tool point.
+   void setToolPoint(const double tool[3]);
+   bool hasToolPoint() const { return _hasTool; }
+   bool kinChain(batotp_kin_chain *out);
+   int chainToolPoint(const Channels &theta, Channels &cart);
    // extension: the trigonometry of the built-in models, spelled out call by call -- it is what the reference's optimised
    // build calls, and the tables the device layer uploads (BATOTP_F_HOST_TRIG) are made with the same helpers.
    //   kinSinCos        one glibc sincos(): "c=cos(t); s=sin(t);" of the forward kinematics (reference robot.cpp:130-136,198-199)
@@ -63,6 +72,8 @@ private:
    Channels _anchors;
    batotp_serial_model _serial;
    bool _hasSerial = false, _serialProbed = false;
+   double _tool[3] = {0, 0, 0};
+   bool _hasTool = false;
    void serialChainDynamics(const batotp_serial_model &m, Channels &a1, Channels &a2, Channels &a3, Channels &a4,
                             const Channels &theta, const Channels &thetaD, const Channels &thetaD2) const;
 

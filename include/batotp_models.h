@@ -1,5 +1,6 @@
 /*
- * batotp_models.h -- built-in serial-chain model tables (data only) for batotp_hip_set_serial_model.
+ * batotp_models.h -- built-in serial-chain model tables (data only) for batotp_hip_set_serial_model, and built-in
+ * kinematic chains (data only) for the tool point of include/batotp_hip_kin.h.
  *
  * The reference hard-codes its robots in Robot::set_robotType (batotp/robot.cpp:51-62) and has a dynamics
  * model for one serial robot only, the two-link arm (Robot::dynRR, robot.cpp:377-431).  BASELINE config 3
@@ -14,6 +15,7 @@
 
 #include <string.h>
 #include "batotp_hip.h"
+#include "batotp_hip_kin.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -61,6 +63,63 @@ static inline int batotp_builtin_serial_model(int robot_type, batotp_serial_mode
         m->gravity[1] = -9.81;
         batotp_model_link(&m->link[0], 0, 0, 1,   0, 0, 0,     0.2, 0, 0,   4.0, 0, 0, 0, 10.0);
         batotp_model_link(&m->link[1], 0, 0, 1,   0.4, 0, 0,   0.3, 0, 0,   8.0, 0, 0, 0, 10.0);
+        return 0;
+    }
+    return -1;
+}
+
+/* axes and offsets of a dynamics model plus a tool point (relative to the last joint origin) as a kinematic chain
+ * (include/batotp_hip_kin.h) */
+static inline void batotp_kin_chain_of_model(const batotp_serial_model *m, const double tool[3], batotp_kin_chain *c)
+{
+    int i, j;
+    memset(c, 0, sizeof(*c));
+    c->n_links = m->n_links;
+    c->degrees = m->degrees;
+    for (i = 0; i < m->n_links && i < BATOTP_MAX_LINKS; ++i)
+        for (j = 0; j < 3; ++j) { c->axis[i][j] = m->link[i].axis[j]; c->off[i][j] = m->link[i].off[j]; }
+    for (j = 0; j < 3; ++j) c->tool[j] = tool[j];
+}
+
+static inline void batotp_chain_link(batotp_kin_chain *c, int i, double ax, double ay, double az, double ox, double oy, double oz)
+{
+    c->axis[i][0] = ax; c->axis[i][1] = ay; c->axis[i][2] = az;
+    c->off[i][0] = ox; c->off[i][1] = oy; c->off[i][2] = oz;
+}
+
+/* Fills *c for BATOTP_ROBOT_KUKA and BATOTP_ROBOT_RR (the chains of the tables above with the tool points of Robot::fwdKinKuka,
+ * robot.cpp:113, and of Robot::fwdKinRR, robot.cpp:198-199: the second link's length) or BATOTP_ROBOT_UR: a UR5 with the NOMINAL
+ * Denavit-Hartenberg parameters its maker publishes (d1 = .089159, a2 = -.425, a3 = -.39225, d4 = .10915, d5 = .09465,
+ * d6 = .0823), restated in zero-aligned frames; a real arm differs from them by its calibration, millimetres at the tool.
+ * All three take joint values in degrees.  Returns 0, or -1 for a robot type without a table. */
+static inline int batotp_builtin_kin_chain(int robot_type, batotp_kin_chain *c)
+{
+    batotp_serial_model m;
+    memset(c, 0, sizeof(*c));
+    if (robot_type == BATOTP_ROBOT_KUKA && batotp_builtin_serial_model(robot_type, &m) == 0)
+    {
+        const double tool[3] = {0, -.08, .545};
+        batotp_kin_chain_of_model(&m, tool, c);
+        return 0;
+    }
+    if (robot_type == BATOTP_ROBOT_RR && batotp_builtin_serial_model(robot_type, &m) == 0)
+    {
+        const double tool[3] = {.6, 0, 0};
+        batotp_kin_chain_of_model(&m, tool, c);
+        return 0;
+    }
+    if (robot_type == BATOTP_ROBOT_UR)
+    {
+        c->n_links = 6;
+        c->degrees = 1;
+        /*                      axis         offset from parent joint */
+        batotp_chain_link(c, 0, 0, 0, 1,    0, 0, 0);
+        batotp_chain_link(c, 1, 0, -1, 0,   0, 0, .089159);
+        batotp_chain_link(c, 2, 0, -1, 0,   -.425, 0, 0);
+        batotp_chain_link(c, 3, 0, -1, 0,   -.39225, 0, 0);
+        batotp_chain_link(c, 4, 0, 0, -1,   0, -.10915, 0);
+        batotp_chain_link(c, 5, 0, -1, 0,   0, 0, -.09465);
+        c->tool[0] = 0; c->tool[1] = -.0823; c->tool[2] = 0;
         return 0;
     }
     return -1;
