@@ -192,6 +192,7 @@ class BatotpError(RuntimeError):
 
 # ---- audit of finished trajectories (include/batotp_hip_audit.h) -------------------------------------------------------
 AUDIT_BLOCK_POINTS = 1024   # BATOTP_AUDIT_BLOCK_POINTS: points per workgroup of the audit kernel
+INVDYN_BLOCK_POINTS = 128   # BATOTP_INVDYN_BLOCK_POINTS (include/batotp_hip_invdyn.h): points per workgroup of the torque kernel
 AUDIT_JNT_VEL, AUDIT_JNT_ACC, AUDIT_CART_VEL, AUDIT_CART_ACC, AUDIT_TRQ = range(5)
 AUDIT_FAMILIES = ("JNT_VEL", "JNT_ACC", "CART_VEL", "CART_ACC", "TRQ")
 
@@ -342,6 +343,24 @@ class Library:
                 fn = getattr(L, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
+
+        # ... and of include/batotp_hip_invdyn.h (torque rows for finished trajectories), likewise
+        invdyn_sig = {
+            "batotp_hip_output_torques": [P, C.POINTER(SerialModel), C.c_uint32, C.POINTER(P)],
+            "batotp_hip_output_torques_ms": [P, C.POINTER(C.c_float)],
+            "batotp_hip_output_torques_ranges": [P, C.POINTER(I32)],
+        }
+        self.invdyn_symbols = sorted(invdyn_sig)
+        self.has_invdyn = all(hasattr(L, name) for name in invdyn_sig)
+        if self.has_invdyn:
+            for name, argtypes in invdyn_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_invdyn(self):
+        if not self.has_invdyn:
+            raise BatotpError(f"{self.path} does not export the inverse-dynamics entry points (include/batotp_hip_invdyn.h)")
 
     def need_kin(self):
         if not self.has_kin:
@@ -628,6 +647,34 @@ class Output:
         v = C.c_float(0)
         self.L.check(self.lib.batotp_hip_output_audit_ms(self.handle, C.byref(v)), "output_audit_ms")
         return float(v.value)
+
+    def torques(self, model: SerialModel, host_trig: bool = True, flags: Optional[int] = None) -> "Output":
+        """a NEW Output: these joint and Cartesian rows followed by model.n_links torque rows, the inverse dynamics of the chain
+        model at every output point (batotp_hip_output_torques, include/batotp_hip_invdyn.h).  host_trig: cos / sin from the host
+        libm (bit parity with tests/invdyn_reference.py), else the device libm; flags overrides it with a raw flag word"""
+        self.L.need_invdyn()
+        new = Output.__new__(Output)
+        new.lib, new.L = self.lib, self.L
+        new.n_paths, new.n_joints = self.n_paths, self.n_joints
+        new.handle = C.c_void_p()
+        f = (F_HOST_TRIG if host_trig else 0) if flags is None else int(flags)
+        self.L.check(self.lib.batotp_hip_output_torques(self.handle, C.byref(model), f, C.byref(new.handle)), "batotp_hip_output_torques")
+        new._read_info()
+        return new
+
+    def torques_ms(self) -> float:
+        """milliseconds of the torque kernels of the call that made this Output (Output.torques)"""
+        self.L.need_invdyn()
+        v = C.c_float(0)
+        self.L.check(self.lib.batotp_hip_output_torques_ms(self.handle, C.byref(v)), "output_torques_ms")
+        return float(v.value)
+
+    def torques_ranges(self) -> int:
+        """ranges of paths the call that made this Output was cut into (workspace budget)"""
+        self.L.need_invdyn()
+        v = C.c_int32(0)
+        self.L.check(self.lib.batotp_hip_output_torques_ranges(self.handle, C.byref(v)), "output_torques_ranges")
+        return int(v.value)
 
     def close(self):
         if self.handle:

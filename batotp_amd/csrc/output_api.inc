@@ -16,6 +16,9 @@ struct batotp_output
    float ms = 0.f;
    float auditMs = 0.f;         // kernels of the last audit of these rows (audit_api.inc)
    bool audited = false;
+   bool fromTorques = false;    // made by batotp_hip_output_torques (invdyn_api.inc) ...
+   float trqMs = 0.f;           // ... kernels of that call
+   int trqRanges = 0;           // ... and the ranges of paths it was cut into
 };
 
 extern "C" int batotp_hip_output_destroy(batotp_output *o)

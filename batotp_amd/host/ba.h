@@ -202,6 +202,14 @@ public:
    void setAuditTolerance(double tol);
    // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: audit off)
    const std::vector<BatchAudit> &getLastAudit() const { return _lastAudit; }
+   // Extension: torque rows for trajectories planned WITHOUT torque limits (include/batotp_hip_invdyn.h): with this on,
+   // optimizeBatch() fills Traj::trq of every path of a serial robot whose torque constraint is off with the inverse dynamics
+   // of the chain model (setSerialModel, or the built-in KUKA table) along the finished samples, while the range's
+   // trajectories are still in device memory and before the audit.  An audit (setAuditTolerance) then covers the torque
+   // rows too, against the configuration's jntTrqMax / jntTrqMin.  Without a model optimizeBatch() returns -1 with a message;
+   // paths planned WITH torque limits keep the output stage's own torque rows.  Off by default (nothing changes).  Defined
+   // in ba_invdyn.cpp, the only file of the library that refers to the entry points of that header.
+   void setOutputTorques(bool on);
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
    // traj.sres and the knot count in traj.nPts.  No device call.
@@ -380,6 +388,8 @@ private:
    // audits the n paths of a batotp_output with a batotp_problem; set by setAuditTolerance (ba_audit.cpp)
    int (*_auditFn)(void *output, const void *problem, double tol, size_t n, BatchAudit *out) = nullptr;
    std::vector<BatchAudit> _lastAudit;
+   // batotp_hip_output_torques behind a pointer; set by setOutputTorques (ba_invdyn.cpp)
+   int (*_torquesFn)(void *output, const void *model, unsigned int flags, void **out) = nullptr;
    // batotp_hip_resample_chain / batotp_hip_set_kin_chain behind pointers; set by setToolPoint (ba_kin.cpp)
    int (*_kinResampleFn)(void *ctx, const void *params, const void *chain, int nPaths, const int64_t *nIn, const double *x, const double *sresIn,
                          void **out) = nullptr;

@@ -976,6 +976,13 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       printf("optimizeBatch(): the interpolate-only mode and paths whose s is the teach time go through optimize(), one path at a time.\n");
       return -1;
    }
+   // torque rows for paths planned without torque limits (setOutputTorques): inverse dynamics of the chain model
+   const bool addTorques = _torquesFn && !_isTrqConOn && !_isParallelMechOrig;
+   if (addTorques && !myRobot.serialModel())
+   {
+      printf("optimizeBatch(): torque rows were asked for (setOutputTorques) but there is no dynamics model for robotType=%s.\n", _robotTypeStr.c_str());
+      return -1;
+   }
    if (gpuAcquire() != 0) return -1;
 
    std::vector<int> ok(trajs.size(), 0);
@@ -1277,6 +1284,16 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       }
       if (rc) return fail("output", rc);
       ++outputCalls;
+      if (addTorques)
+      {
+         // the range's rows with the torques of the chain model appended, while they are in device memory (host trig tables:
+         // the bits of the definition, include/batotp_hip_invdyn.h)
+         void *withTrq = nullptr;
+         rc = _torquesFn(og.o, myRobot.serialModel(), BATOTP_F_HOST_TRIG, &withTrq);
+         if (rc) return fail("output_torques", rc);
+         batotp_hip_output_destroy(og.o);
+         og.o = static_cast<batotp_output *>(withTrq);
+      }
       nPtsOut.assign(cnt, 0);
       sresOut.assign(cnt, 0.0);
       rc = batotp_hip_output_info(og.o, nPtsOut.data(), sresOut.data());
@@ -1297,7 +1314,20 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       {
          // the trajectories of the range against the limits, while they are still in device memory
          std::vector<BatchAudit> audit(cnt);
-         rc = _auditFn(og.o, &prob, _auditTol, cnt, audit.data());
+         batotp_problem probAudit = prob;
+         if (addTorques)
+         {
+            // the torque rows against the configuration's jntTrqMax / jntTrqMin (a configuration without a torque range keeps
+            // the family off: the audit refuses a range that is not finite and positive)
+            bool haveRange = true;
+            for (unsigned int j = 0; j < _nJoints && j < BATOTP_MAX_JOINTS; ++j)
+            {
+               const double half = (prob.jnt_trq_max[j] - prob.jnt_trq_min[j]) * 0.5;
+               haveRange = haveRange && std::isfinite(half) && half > 0.0;
+            }
+            if (haveRange) probAudit.flags |= BATOTP_F_TRQ_ON;
+         }
+         rc = _auditFn(og.o, &probAudit, _auditTol, cnt, audit.data());
          if (rc) return fail("output_audit", rc);
          for (size_t q = 0; q < cnt; ++q) _lastAudit[live[k0 + q]] = audit[q];
       }
@@ -1314,6 +1344,13 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          if (n == 0) { ok[live[k]] = 0; continue; }
          _nCart = (rsp.path_type == BATOTP_PATH_BOTH && nCartTaught == 6) ? 7 : nCartTaught;
          unpackOutputRows(t, flatAll.data() + at, n, nTh, nCa, nTq, sresOut[q], r.n_fwd, r.t_total, (r.status_fwd & BATOTP_ST_SHORT) != 0, h);
+         if (addTorques && nCa == 0)
+         {
+            // (unpackOutputRows reads torque rows only beside Cartesian rows, as the output stage makes them)
+            const double *trqRows = flatAll.data() + at + (size_t)nTh * (size_t)n;
+            t.trq.assign(_nJoints, std::vector<double>());
+            for (int j = 0; j < nTq; ++j) t.trq[j].assign(trqRows + (size_t)j * n, trqRows + (size_t)(j + 1) * n);
+         }
          at += (size_t)n * rows;
          if (is_sdotOut)
          {

@@ -1,11 +1,14 @@
 // batest_batch_main.cpp -- command-line driver of the many-path extension BA::optimizeBatch().
 //
-//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]]
+//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques]
 //
 // --audit [tol] (builds with -DBATOTP_HAVE_AUDIT, i.e. the product's): the finished trajectories are audited against the
 // limits on the device (BA::setAuditTolerance, include/batotp_hip_audit.h; tol defaults to 0) and one summary line names
 // the worst peak of every family with its path and time, and the paths with points over 1 + tol.  Exit status 4 if a
 // trajectory holds a value that is not finite.
+// --torques (builds with -DBATOTP_HAVE_INVDYN, i.e. the product's): paths planned without torque limits get torque rows from the
+// inverse dynamics of the chain model along the finished samples (BA::setOutputTorques, include/batotp_hip_invdyn.h); with
+// --audit one more line per path gives the peak utilisation of the configuration's torque range.
 // --auto-integ-res leaves BA's class default on (reference ba.h:309; the reference's own driver switches it off,
 // test/main.cpp:53): every path then integrates with the step the rule of ba.cpp:493-556 derives from it.
 // (--host-resample / --host-output are accepted and ignored: since round 4 both stages always run behind the C-ABI.)
@@ -28,7 +31,7 @@ int main(int argc, char *argv[])
 {
    if (argc < 3)
    {
-      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices]\n");
+      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques]\n");
       return 2;
    }
    const int nPaths = atoi(argv[2]);
@@ -38,8 +41,14 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_AUDIT
    double auditTol = -1;
 #endif
+#ifdef BATOTP_HAVE_INVDYN
+   bool torques = false;
+#endif
    for (int k = 3; k < argc; ++k)
    {
+#ifdef BATOTP_HAVE_INVDYN
+      if (std::string(argv[k]) == "--torques") torques = true;
+#endif
 #ifdef BATOTP_HAVE_AUDIT
       if (std::string(argv[k]) == "--audit")
       {
@@ -70,6 +79,9 @@ int main(int argc, char *argv[])
    if (planner.readConfigData((std::string("./") + argv[1]).c_str()) == -1) return 1;
 #ifdef BATOTP_HAVE_AUDIT
    planner.setAuditTolerance(auditTol);
+#endif
+#ifdef BATOTP_HAVE_INVDYN
+   planner.setOutputTorques(torques);
 #endif
    if (allDevices) nDevices = planner.useAllDevices();
    else if (nDevices > 0)
@@ -115,6 +127,15 @@ int main(int argc, char *argv[])
       }
       printf(nOverPaths ? "\n" : " none\n");
       if (nonfinite) printf("audit: a trajectory holds values that are not finite\n");
+#ifdef BATOTP_HAVE_INVDYN
+      if (torques)
+         for (size_t p = 0; p < audit.size(); ++p)
+         {
+            if (!audit[p].audited) printf("torques: path %d not audited\n", (int)p);
+            else if (audit[p].peak[4] < 0) printf("torques: path %d trq -\n", (int)p);
+            else printf("torques: path %d trq %.6f (t %.6f s, row %d)\n", (int)p, audit[p].peak[4], (double)audit[p].at[4] * audit[p].sres, audit[p].row[4]);
+         }
+#endif
    }
 #endif
 
