@@ -24,6 +24,7 @@
 #pragma once
 #include "kernels.hip.h"
 #include "mvc_window.h"
+#include "knot_window.h"
 
 // diagnostic build (-DS8_PROFILE): what a wavefront of k_sweep8 spends its passes and cycles on, 16 doubles per wavefront in
 // SweepArgs::prof (tools/sweep8_sections.py); no effect otherwise
@@ -52,6 +53,10 @@ constexpr int S8_BLOCK = 256;
 //   kept: the reverse curve around the cursor in registers, its loads off the stage's dependent chain (mvc_window.h; forward launch of
 //         the headline 1655 -> 1537 ms in k_sweep8_lock, profiles/fwd_curve_window_*).  (Round 4's prefetch of the next point alone, selected
 //         into place per lane, had measured 5 % slower -- 440 against 419 ms: the select waits for the load where it stands.)
+//   kept: the knots of the compact layout as a register window around the knot cursor, the load of the knot beyond issued by every lane
+//         of a segment-change block and first read by the next such block (knot_window.h; both directions, G = 8 and 4, and k_sweep8_lock:
+//         headline reverse launch 3015 -> 2854 ms, forward launch 1538 -> 1410 ms, profiles/knot_window_*).  The knots are held as four
+//         scalars: the double2 selects of the literal route had cost the FEAT -1 kernels 80 bytes of scratch and two scratch stores per change.
 
 // (num / den) < thr as ratio_lt (kernels.hip.h) decides it, in two parts: the product form, and whether it was decisive
 __device__ __forceinline__ bool s8_ratio_lt_fast(double num, double den, double thr, bool &decided)
@@ -353,13 +358,13 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    const double *__restrict__ coef = t.coef;
    const int rowStride = t.C * 4;
    int seg = t.segC, rowSeg = t.rowSeg;
-   // knot prefetch (compact pairs): the knot on the side the cursor moves to (reverse: knot rowSeg, forward: knot rowSeg + 1)
-   // and the one beyond it, loaded when the cursor entered the current segment -- a segment change one step further then
-   // forms its coefficients from registers and issues the load for the change after it
-   double2 kEdge[PER], kPre[PER];
-   int preIdx = -(1 << 20); // knot index kPre holds (and kEdge holds preIdx - DIR): none yet
+   // knot window (compact pairs, knot_window.h): the knot on the side the cursor moves to (reverse: knot rowSeg, forward: knot
+   // rowSeg + 1) and the one beyond it, as (y, y'') each -- a segment change one step further forms its coefficients from registers;
+   // every segment-change block of the wavefront issues the load of the knot beyond, which nothing reads before the next such block
+   double kEdgeY[PER], kEdgeSol[PER], kPreY[PER], kPreSol[PER];
+   int preIdx = KNOT_WINDOW_NONE; // knot index the prefetch pair holds (and the edge pair holds preIdx - DIR): none yet
 #pragma unroll
-   for (int q = 0; q < PER; ++q) { kEdge[q] = make_double2(0, 0); kPre[q] = make_double2(0, 0); }
+   for (int q = 0; q < PER; ++q) { kEdgeY[q] = 0; kEdgeSol[q] = 0; kPreY[q] = 0; kPreSol[q] = 0; }
    double sSeg = sres * (double)seg, sNext = sres * (double)(seg + 1); // sites of the cursor's segment
    // reverse-curve cursor (forward sweep): segment, its two points and the window's two neighbours (mvc_window.h; indices clamped
    // to the curve)
@@ -633,21 +638,14 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                         if (FEAT < 0)
                         {
                            const unsigned at = (unsigned)(seg * nIn + jAt[q]);
-                           // (declared here, assigned in the blocks below: initialising them at their declaration swaps two register pairs of
-                           //  the validated build, profiles/refactor_code_object_identity.txt)
-                           double2 kl, kr; // knots seg and seg + 1 of this joint
-                           bool literal = false; // the knots are not the prefetched ones, or a sixth lies outside div6's window
-                           {
-                              // one segment further in the direction of the sweep: both knots are in registers
-                              const bool hit = (DIR == 1) ? (preIdx == seg + 1) : (preIdx == seg);
-                              kl = (DIR == 1) ? kEdge[q] : kPre[q];
-                              kr = (DIR == 1) ? kPre[q] : kEdge[q];
-                              literal = !hit;
-                           }
+                           // one segment further in the direction of the sweep: both knots (seg and seg + 1 of this joint) are in registers
+                           // (as four scalars: selecting between double2 values sends them through scratch)
+                           double yL = (DIR == 1) ? kEdgeY[q] : kPreY[q], solL = (DIR == 1) ? kEdgeSol[q] : kPreSol[q];
+                           double yR = (DIR == 1) ? kPreY[q] : kEdgeY[q], solR = (DIR == 1) ? kPreSol[q] : kEdgeSol[q];
+                           bool literal = !knot_window_hit(preIdx, seg, DIR); // the knots are not the window's, or a sixth lies outside div6's window
                            // emit_segment's formulas (spline.cpp:203-209); x / 6 as div6 computes it inside its window, and ONE
                            // wavefront-uniform guard for everything that is rare here (a missed prefetch, a sixth outside the window)
-                           double solL = kl.y, solR = kr.y, yL = kl.x, yR = kr.x;
-                           double xa = solR - solL, xb = solR + 2 * solL;
+                           const double xa = solR - solL, xb = solR + 2 * solL;
                            literal |= !((fabs(xa) > 1e-280) & (fabs(xa) < 1e280) & (fabs(xb) > 1e-280) & (fabs(xb) < 1e280));
                            double c3, sixthB;
                            {
@@ -657,22 +655,14 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                            }
                            if (S8_RARE(literal))
                            {
-                              {
-                                 const bool hit = (DIR == 1) ? (preIdx == seg + 1) : (preIdx == seg);
-                                 const double2 dl = km[at], dr = km[at + nIn];
-                                 kl = hit ? kl : dl;
-                                 kr = hit ? kr : dr;
-                              }
-                              solL = kl.y; solR = kr.y; yL = kl.x; yR = kr.x;
+                              const bool hit = knot_window_hit(preIdx, seg, DIR);
+                              const double2 dl = km[at], dr = km[at + nIn];
+                              yL = hit ? yL : dl.x; solL = hit ? solL : dl.y;
+                              yR = hit ? yR : dr.x; solR = hit ? solR : dr.y;
                               c3 = div6(solR - solL);
                               sixthB = div6(solR + 2 * solL);
                            }
-                           {
-                              kEdge[q] = (DIR == 1) ? kr : kl;
-                              int nxt = (DIR == 1) ? seg + 2 : seg - 1;
-                              nxt = nxt < 0 ? 0 : (nxt > lastSeg + 1 ? lastSeg + 1 : nxt);
-                              kPre[q] = km[(unsigned)(nxt * nIn + jAt[q])];
-                           }
+                           knot_window_shift(true, DIR, yL, solL, yR, solR, kEdgeY[q], kEdgeSol[q]);
                            const double c2 = solL / 2.0;
                            c1[q] = yR - yL - sixthB;
                            c2x2[q] = 2 * c2; c3x3[q] = 3 * c3; c3x6[q] = 6 * c3;
@@ -683,12 +673,20 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                            c1[q] = k.c1; c2x2[q] = 2 * k.c2; c3x3[q] = 3 * k.c3; c3x6[q] = 6 * k.c3;
                         }
                      }
-                     if (FEAT < 0)
-                     {
-                        const int nxt = (DIR == 1) ? seg + 2 : seg - 1;
-                        preIdx = nxt < 0 ? (-(1 << 20)) : (nxt > lastSeg + 1 ? (-(1 << 20)) : nxt); // a clamped prefetch holds no usable knot
-                     }
+                     if (FEAT < 0) preIdx = knot_window_mark(seg, lastSeg, DIR);
                      rowSeg = seg;
+                  }
+                  if (FEAT < 0)
+                  {
+                     // the window's load (knot_window.h): every lane of the block, changed or not, straight into the prefetch registers;
+                     // the next segment-change block of the wavefront is the first to read them
+                     const int at = knot_window_load(seg, lastSeg, DIR) * nIn;
+#pragma unroll
+                     for (int q = 0; q < PER; ++q)
+                     {
+                        const double2 kq = km[(unsigned)(at + jAt[q])];
+                        kPreY[q] = kq.x; kPreSol[q] = kq.y;
+                     }
                   }
                }
                {

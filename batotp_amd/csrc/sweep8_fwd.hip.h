@@ -16,12 +16,13 @@
 //     and reads all five back at the start of the next one); a failed bisection leaves w_st of the previous step as it was;
 //   * after the prologue of a stage ONE constraint check runs for all live paths; only if one of them is violated does the
 //     bisection loop run, until every path of the wavefront has ended the stage.
-// Kept as they are: the knot-cursor walk, the segment change with its prefetched knots, sweep8_mvcwalk.inc (the walk of the
-// reverse-curve cursor over its register window, mvc_window.h: the one fragment both kernels include), the margin for curves in
+// Kept as they are: the knot-cursor walk, the segment change over its window of two knots (knot_window.h, shared with k_sweep8: the
+// load of the knot beyond is issued by every live lane and first read by the wavefront's next segment change), sweep8_mvcwalk.inc (the walk
+// of the reverse-curve cursor over its register window, mvc_window.h: the one fragment both kernels include), the margin for curves in
 // place, the staging of four curve points in LDS, the certified fast-forward (s8_certify), the end snap, the short-curve tail and
 // the result row.
-// The arithmetic is a COPY of k_sweep8's with G = 8, DIR = +1 (sweep8.hip.h may not change: its code object is the validated one, and a
-// shared fragment other than the walk would have to leave it byte for byte as it is).  A change on either side belongs on both:
+// The arithmetic is a COPY of k_sweep8's with G = 8, DIR = +1 (shared are the walk's fragment and the two window headers, mvc_window.h and
+// knot_window.h; a shared fragment of anything else would have to leave k_sweep8's code as it is).  A change on either side belongs on both:
 //   here                                        sweep8.hip.h, k_sweep8
 //   setup, bootstrap, loop state                "stage_limits" .. "const int hold = a.hold" (lane mapping to the S8_PROFILE block)
 //   checkPass                                   the block `if (phase == PH_CHECK)`: check, one pass of the bisection, s8_certify
@@ -130,9 +131,9 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    const double *__restrict__ coef = t.coef;
    const int rowStride = t.C * 4;
    int seg = t.segC, rowSeg = t.rowSeg;
-   // knot prefetch (compact pairs): knot rowSeg + 1 and the one beyond it, loaded when the cursor entered the current segment
-   double2 kEdge = make_double2(0, 0), kPre = make_double2(0, 0);
-   int preIdx = -(1 << 20); // knot index kPre holds (and kEdge holds preIdx - 1): none yet
+   // knot window (compact pairs, knot_window.h): knot rowSeg + 1 and the one beyond it, as (y, y'') each
+   double kEdgeY = 0, kEdgeSol = 0, kPreY = 0, kPreSol = 0;
+   int preIdx = KNOT_WINDOW_NONE; // knot index the prefetch pair holds (and the edge pair holds preIdx - 1): none yet
    // reverse-curve cursor: segment, its two points and the window's two neighbours (mvc_window.h; indices clamped to the curve)
    int segM = t.segMVC;
    double mS0, mD0, mS1, mD1, mSLo, mDLo, mSHi, mDHi;
@@ -358,8 +359,8 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
                      const unsigned at = (unsigned)(seg * nIn + jAt);
                      // one segment further in the direction of the sweep: both knots (seg and seg + 1 of this joint) are in registers
                      // (as four scalars: selecting between double2 values sends them through scratch)
-                     double yL = kEdge.x, solL = kEdge.y, yR = kPre.x, solR = kPre.y;
-                     bool literal = !(preIdx == seg + 1); // the knots are not the prefetched ones, or a sixth lies outside div6's window
+                     double yL = kEdgeY, solL = kEdgeSol, yR = kPreY, solR = kPreSol;
+                     bool literal = !knot_window_hit(preIdx, seg, DIR); // the knots are not the window's, or a sixth lies outside div6's window
                      // emit_segment's formulas (spline.cpp:203-209); x / 6 as div6 computes it inside its window, and ONE
                      // wavefront-uniform guard for everything that is rare here (a missed prefetch, a sixth outside the window)
                      const double xa = solR - solL, xb = solR + 2 * solL;
@@ -372,24 +373,18 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
                      }
                      if (S8_RARE(literal))
                      {
-                        const bool hit = (preIdx == seg + 1);
+                        const bool hit = knot_window_hit(preIdx, seg, DIR);
                         const double2 dl = km[at], dr = km[at + nIn];
                         yL = hit ? yL : dl.x; solL = hit ? solL : dl.y;
                         yR = hit ? yR : dr.x; solR = hit ? solR : dr.y;
                         c3 = div6(solR - solL);
                         sixthB = div6(solR + 2 * solL);
                      }
-                     {
-                        kEdge = make_double2(yR, solR);
-                        int nxt = seg + 2;
-                        nxt = nxt < 0 ? 0 : (nxt > lastSeg + 1 ? lastSeg + 1 : nxt);
-                        kPre = km[(unsigned)(nxt * nIn + jAt)];
-                     }
+                     knot_window_shift(true, DIR, yL, solL, yR, solR, kEdgeY, kEdgeSol);
                      const double c2 = solL / 2.0;
                      c1 = yR - yL - sixthB;
                      c2x2 = 2 * c2; c3x3 = 3 * c3; c3x6 = 6 * c3;
-                     const int nxt = seg + 2;
-                     preIdx = nxt < 0 ? (-(1 << 20)) : (nxt > lastSeg + 1 ? (-(1 << 20)) : nxt); // a clamped prefetch holds no usable knot
+                     preIdx = knot_window_mark(seg, lastSeg, DIR);
                   }
                   else
                   {
@@ -397,6 +392,13 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
                      c1 = k.c1; c2x2 = 2 * k.c2; c3x3 = 3 * k.c3; c3x6 = 6 * k.c3;
                   }
                   rowSeg = seg;
+               }
+               if (FEAT < 0)
+               {
+                  // the window's load (knot_window.h): every live lane, changed or not, straight into the prefetch registers; the next
+                  // segment-change block of the wavefront is the first to read them
+                  const double2 kq = km[(unsigned)(knot_window_load(seg, lastSeg, DIR) * nIn + jAt)];
+                  kPreY = kq.x; kPreSol = kq.y;
                }
             }
             {
