@@ -154,6 +154,13 @@ CASES = {
     # input decimation + smoothing (ba.cpp:195-242)
     "synth_gen7dof_s10_decim": (synth_gen7dof(10, 45, decim=3, smooth=3), True),
     "synth_cspr_s11_decim": (synth_cspr(11, 14, decim=2), True),
+    # wide windows (factor >= 5: the shrinking-window branches of smooth(), half width 2 and 4), also on a pose path and on
+    # the robots with forward kinematics
+    "synth_gen7dof_s23_decim9": (synth_gen7dof(23, 12, repeat_every=4, decim=9, smooth=2), True),
+    "synth_cspr_s22_decim5": (synth_cspr(22, 14, decim=5, smooth=2), True),
+    "UR5_decim5": (shipped("UR5", {"inputDecimFact": 5, "smoothWindow": 3}), True),
+    "RR_decim5": (shipped("RR", {"inputDecimFact": 5, "smoothWindow": 3}), True),
+    "KUKA_decim5": (shipped("KUKA-LWR-IV", {"inputDecimFact": 5, "smoothWindow": 3}), True),
     # s = teach time (sWeights 1 0 0: adjust_s returns at once, ba.cpp:416): the knots are the taught points after close-point
     # removal, input smoothing / decimation -- the branch the host library keeps (BA::keepTaughtSpacing with the filters of
     # batotp_amd/host/util.cpp); repeated points so that remClosePts really thins the path, the last one repeated too

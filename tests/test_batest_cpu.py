@@ -31,7 +31,7 @@ def _stage(src, dst):
 
 
 @pytest.mark.parametrize("name", ["synth_cspr_s3", "synth_gen7dof_s1_vel", "synth_ur_s2", "GEN7DOF", "UR5", "UR5_pos3", "RR", "RR_acc", "KUKA-LWR-IV", "KUKA_cartacc",
-                                  "CSPR3DOF", "CSPR3DOF_svd", "synth_gen7dof_s10_decim", "synth_cspr_s9_dup"])
+                                  "CSPR3DOF", "CSPR3DOF_svd", "synth_gen7dof_s10_decim", "synth_cspr_s9_dup", "UR5_decim5", "synth_cspr_s22_decim5"])
 def test_batch_driver_files_equal_reference(tmp_path, oracle_lib, name):
     """BA::optimizeBatch (the many-path extension) writes, for every copy of the path, the files the reference binary wrote for
     the single path -- resampling (batotp_hip_resample) and output stage (batotp_hip_output) behind the C-ABI"""

@@ -114,7 +114,9 @@ def test_which_configurations_the_device_stages_cover():
                                            # the cable robot with solveLinSys through the Jacobi SVD (isSVD = 1)
                                            "CSPR3DOF_svd", "CSPR3DOF_par_svd",
                                            # round 6: joints and tool POSITIONS taught together (path type BOTH with nCart = 3, no orientations)
-                                           "UR5_pos3"}
+                                           "UR5_pos3",
+                                           # input decimation factors 5 and 9: the wide windows of the input smoothing
+                                           "synth_gen7dof_s23_decim9", "synth_cspr_s22_decim5", "UR5_decim5", "RR_decim5", "KUKA_decim5"}
     # paths whose s is the teach time (sWeights 1 0 0) need no resampling stage: adjust_s returns at once (ba.cpp:416) and the
     # knots are the taught points after the host filters (BA::keepTaughtSpacing); the output stage runs on the device for them too
     teach_time = {"synth_gen7dof_s14_teachtime", "synth_gen7dof_s15_teachtime_decim2"}
