@@ -212,6 +212,21 @@ AUDIT_DTYPE = np.dtype([("fam", [("peak", "<f8"), ("at", "<i8"), ("row", "<i4"),
 assert AUDIT_DTYPE.itemsize == C.sizeof(PathAudit)
 
 
+# ---- stretching finished trajectories in time (include/batotp_hip_stretch.h) ----------------------------------------------
+STRETCH_BLOCK_POINTS = 256          # BATOTP_STRETCH_BLOCK_POINTS: new points per workgroup of the stretch kernel
+STRETCH_MAX_POINTS = 1 << 40        # BATOTP_STRETCH_MAX_POINTS
+STRETCH_PASSES, STRETCH_ROUNDS, STRETCH_CAPPED = 0, 1, 2
+
+
+class PathStretch(C.Structure):
+    """struct batotp_path_stretch"""
+    _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("factor", C.c_double), ("rounds", C.c_int32), ("status", C.c_int32)]
+
+
+STRETCH_DTYPE = np.dtype([("n_in", "<i8"), ("n_out", "<i8"), ("factor", "<f8"), ("rounds", "<i4"), ("status", "<i4")])
+assert STRETCH_DTYPE.itemsize == C.sizeof(PathStretch) == 32
+
+
 def _dptr(a: Optional[np.ndarray]):
     if a is None:
         return None
@@ -357,6 +372,26 @@ class Library:
                 fn = getattr(L, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
+
+        # ... and of include/batotp_hip_stretch.h (finished trajectories stretched in time), likewise
+        stretch_sig = {
+            "batotp_hip_output_stretch_to": [P, C.POINTER(C.c_int64), C.POINTER(P)],
+            "batotp_hip_output_stretch_by": [P, D, C.POINTER(P)],
+            "batotp_hip_output_stretch_audit": [P, C.POINTER(Problem), C.c_double, I32, C.c_double, C.POINTER(P), C.c_void_p],
+            "batotp_hip_output_stretch_ms": [P, C.POINTER(C.c_float)],
+            "batotp_hip_output_stretch_ranges": [P, C.POINTER(I32)],
+        }
+        self.stretch_symbols = sorted(stretch_sig)
+        self.has_stretch = all(hasattr(L, name) for name in stretch_sig)
+        if self.has_stretch:
+            for name, argtypes in stretch_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_stretch(self):
+        if not self.has_stretch:
+            raise BatotpError(f"{self.path} does not export the stretch entry points (include/batotp_hip_stretch.h)")
 
     def need_invdyn(self):
         if not self.has_invdyn:
@@ -674,6 +709,60 @@ class Output:
         self.L.need_invdyn()
         v = C.c_int32(0)
         self.L.check(self.lib.batotp_hip_output_torques_ranges(self.handle, C.byref(v)), "output_torques_ranges")
+        return int(v.value)
+
+    def _like(self) -> "Output":
+        new = Output.__new__(Output)
+        new.lib, new.L = self.lib, self.L
+        new.n_paths, new.n_joints = self.n_paths, self.n_joints
+        new.handle = C.c_void_p()
+        return new
+
+    def stretch_to(self, n_out) -> "Output":
+        """a NEW Output: the same paths with n_out[k] >= n_pts[k] points at the same time step, the Catmull-Rom cubic through
+        these rows (batotp_hip_output_stretch_to, include/batotp_hip_stretch.h)"""
+        self.L.need_stretch()
+        n2 = np.ascontiguousarray(n_out, dtype=np.int64)
+        assert n2.shape == (self.n_paths,), (n2.shape, self.n_paths)
+        new = self._like()
+        self.L.check(self.lib.batotp_hip_output_stretch_to(self.handle, n2.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(new.handle)),
+                     "batotp_hip_output_stretch_to")
+        new._read_info()
+        return new
+
+    def stretch_by(self, factor) -> "Output":
+        """stretch_to with n_out[k] = ceil((n_pts[k] - 1) * factor[k]) + 1; factor: one value for all paths or one per path"""
+        self.L.need_stretch()
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(factor, dtype=np.float64), (self.n_paths,)))
+        new = self._like()
+        self.L.check(self.lib.batotp_hip_output_stretch_by(self.handle, _dptr(f), C.byref(new.handle)), "batotp_hip_output_stretch_by")
+        new._read_info()
+        return new
+
+    def stretch_audit(self, prob: Problem, target: float = 1.0, max_rounds: int = 8, max_factor: float = 16.0):
+        """(a NEW Output, report): every path stretched, each by its own factor, until its audit against prob has every velocity
+        and acceleration peak <= target (batotp_hip_output_stretch_audit); report is one STRETCH_DTYPE row per path"""
+        self.L.need_stretch()
+        new = self._like()
+        report = np.zeros(self.n_paths, dtype=STRETCH_DTYPE)
+        self.L.check(self.lib.batotp_hip_output_stretch_audit(self.handle, C.byref(prob), float(target), int(max_rounds), float(max_factor),
+                                                              C.byref(new.handle), report.ctypes.data_as(C.c_void_p)),
+                     "batotp_hip_output_stretch_audit")
+        new._read_info()
+        return new, report
+
+    def stretch_ms(self) -> float:
+        """milliseconds of the stretch kernels of the call that made this Output"""
+        self.L.need_stretch()
+        v = C.c_float(0)
+        self.L.check(self.lib.batotp_hip_output_stretch_ms(self.handle, C.byref(v)), "output_stretch_ms")
+        return float(v.value)
+
+    def stretch_ranges(self) -> int:
+        """kernel launches (ranges of paths, over all rounds) of the call that made this Output"""
+        self.L.need_stretch()
+        v = C.c_int32(0)
+        self.L.check(self.lib.batotp_hip_output_stretch_ranges(self.handle, C.byref(v)), "output_stretch_ranges")
         return int(v.value)
 
     def close(self):

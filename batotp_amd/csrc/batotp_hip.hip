@@ -29,6 +29,7 @@
 #include "audit.hip.h"
 #include "kin_chain.hip.h"
 #include "invdyn.hip.h"
+#include "stretch.hip.h"
 
 // Lanes per workgroup of a lane-per-series Thomas solve outside the hot path (resampler, output stage).  Every lane walks its own
 // stream, so a load or store instruction costs its compute unit's address path one cycle per line it touches on top of a fixed ~20
@@ -1902,3 +1903,4 @@ extern "C" int batotp_hip_batch_bytes(batotp_batch *b, int64_t *bytes)
 #include "audit_api.inc"
 #include "kin_api.inc"
 #include "invdyn_api.inc"
+#include "stretch_api.inc"

@@ -19,6 +19,9 @@ struct batotp_output
    bool fromTorques = false;    // made by batotp_hip_output_torques (invdyn_api.inc) ...
    float trqMs = 0.f;           // ... kernels of that call
    int trqRanges = 0;           // ... and the ranges of paths it was cut into
+   bool fromStretch = false;    // made by batotp_hip_output_stretch_to / _by / _audit (stretch_api.inc) ...
+   float stretchMs = 0.f;       // ... stretch kernels of that call, all rounds and ranges
+   int stretchRanges = 0;       // ... and how many launches that was
 };
 
 extern "C" int batotp_hip_output_destroy(batotp_output *o)

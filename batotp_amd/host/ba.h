@@ -143,6 +143,18 @@ struct BatchAudit
    bool audited = false;                       // false: the path failed before the output stage
 };
 
+// Extension: what the time stretch did to one finished trajectory (BA::getLastStretch; the fields of batotp_path_stretch,
+// include/batotp_hip_stretch.h).
+struct BatchStretch
+{
+   long long nIn = 0, nOut = 0; // points before and after
+   double factor = 1.;          // (nOut - 1) / (nIn - 1): the duration grew by this
+   int rounds = 0;              // how many times the path was stretched
+   int status = 0;              // 0 passes, 1 rounds exhausted, 2 stopped at the largest factor allowed
+   bool done = false;           // false: the path failed before the output stage, or was skipped
+   bool skipped = false;        // the path carries the output stage's own torque rows and was left as it is
+};
+
 // defaults of BA::Config (reference ba.h:157-161)
 static const std::vector<double> jntVelLims_init(6, 190);
 static const std::vector<double> jntAccLims_init(6, 500);
@@ -210,6 +222,17 @@ public:
    // paths planned WITH torque limits keep the output stage's own torque rows.  Off by default (nothing changes).  Defined
    // in ba_invdyn.cpp, the only file of the library that refers to the entry points of that header.
    void setOutputTorques(bool on);
+   // Extension: stretch the finished trajectories in time until their audit passes (include/batotp_hip_stretch.h): with a
+   // target in (0, 1], optimizeBatch() dilates every path, each by its own factor, until the joint and Cartesian velocity and
+   // acceleration peaks of its published samples are <= target -- after the output stage, while the range's trajectories are
+   // in device memory, and BEFORE the torque rows (setOutputTorques) and the audit (setAuditTolerance), which then see the
+   // stretched rows, as the Traj arrays do (nPts and tTotalTraj grow by the factor).  maxRounds (1..16) and maxFactor (>= 1)
+   // bound the work per path.  A range whose output carries the stage's own torque rows (torque limits on) is left as it is
+   // and its paths are reported as skipped.  target <= 0 switches it off (default: nothing changes).  Defined in
+   // ba_stretch.cpp, the only file of the library that refers to the entry points of that header.
+   void setStretchToLimits(double target, int maxRounds = 8, double maxFactor = 16.);
+   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: stretch off)
+   const std::vector<BatchStretch> &getLastStretch() const { return _lastStretch; }
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
    // traj.sres and the knot count in traj.nPts.  No device call.
@@ -390,6 +413,12 @@ private:
    std::vector<BatchAudit> _lastAudit;
    // batotp_hip_output_torques behind a pointer; set by setOutputTorques (ba_invdyn.cpp)
    int (*_torquesFn)(void *output, const void *model, unsigned int flags, void **out) = nullptr;
+   // batotp_hip_output_stretch_audit behind a pointer; set by setStretchToLimits (ba_stretch.cpp)
+   double _stretchTarget = 0, _stretchMaxFactor = 16.;
+   int _stretchRounds = 8;
+   int (*_stretchFn)(void *output, const void *problem, double target, int maxRounds, double maxFactor, size_t n, void **out,
+                     BatchStretch *report) = nullptr;
+   std::vector<BatchStretch> _lastStretch;
    // batotp_hip_resample_chain / batotp_hip_set_kin_chain behind pointers; set by setToolPoint (ba_kin.cpp)
    int (*_kinResampleFn)(void *ctx, const void *params, const void *chain, int nPaths, const int64_t *nIn, const double *x, const double *sresIn,
                          void **out) = nullptr;

@@ -855,6 +855,13 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
       for (size_t d = 0; d < nDev; ++d)
          for (size_t q = 0; q < worker[d]._lastAudit.size() && lo[d] + q < lo[d + 1]; ++q) _lastAudit[lo[d] + q] = worker[d]._lastAudit[q];
    }
+   _lastStretch.clear();
+   if (_stretchFn)
+   {
+      _lastStretch.assign(trajs.size(), BatchStretch());
+      for (size_t d = 0; d < nDev; ++d)
+         for (size_t q = 0; q < worker[d]._lastStretch.size() && lo[d] + q < lo[d + 1]; ++q) _lastStretch[lo[d] + q] = worker[d]._lastStretch[q];
+   }
    // what a single-device run leaves in the object (run state a later writeOutputData / interpOutputData reads)
    _isInterpolated = worker[0]._isInterpolated;
    _isParallelMech = worker[0]._isParallelMech;
@@ -970,6 +977,8 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
    setErrorOptimization(NO_ERROR);
    _lastAudit.clear();
    if (_auditFn) _lastAudit.assign(trajs.size(), BatchAudit()); // (setAuditTolerance; a path that fails early keeps audited = false)
+   _lastStretch.clear();
+   if (_stretchFn) _lastStretch.assign(trajs.size(), BatchStretch()); // (setStretchToLimits; likewise done = false)
    if (trajs.empty()) return 0;
    if (_isInterpOnly || _sWeights[1] + _sWeights[2] < 1e-8)
    {
@@ -1284,6 +1293,30 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       }
       if (rc) return fail("output", rc);
       ++outputCalls;
+      if (_stretchFn)
+      {
+         // the range's paths dilated in time until their audit passes, while they are in device memory: the torque rows, the
+         // audit and the Traj arrays below take the stretched rows.  Torques are no function of the path alone, so a range
+         // that carries the stage's own torque rows is left as it is.
+         int32_t sTh = 0, sCa = 0, sTq = 0;
+         rc = batotp_hip_output_channels(og.o, &sTh, &sCa, &sTq);
+         if (rc) return fail("output_channels", rc);
+         if (sTq > 0)
+            for (size_t q = 0; q < cnt; ++q) _lastStretch[live[k0 + q]].skipped = true;
+         else
+         {
+            float msStage = 0;
+            batotp_hip_output_ms(og.o, &msStage); // timing only (the stretched output is not the stage's)
+            kernelMs += msStage;
+            std::vector<BatchStretch> report(cnt);
+            void *stretched = nullptr;
+            rc = _stretchFn(og.o, &prob, _stretchTarget, _stretchRounds, _stretchMaxFactor, cnt, &stretched, report.data());
+            if (rc) return fail("output_stretch_audit", rc);
+            batotp_hip_output_destroy(og.o);
+            og.o = static_cast<batotp_output *>(stretched);
+            for (size_t q = 0; q < cnt; ++q) _lastStretch[live[k0 + q]] = report[q];
+         }
+      }
       if (addTorques)
       {
          // the range's rows with the torques of the chain model appended, while they are in device memory (host trig tables:
@@ -1344,6 +1377,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          if (n == 0) { ok[live[k]] = 0; continue; }
          _nCart = (rsp.path_type == BATOTP_PATH_BOTH && nCartTaught == 6) ? 7 : nCartTaught;
          unpackOutputRows(t, flatAll.data() + at, n, nTh, nCa, nTq, sresOut[q], r.n_fwd, r.t_total, (r.status_fwd & BATOTP_ST_SHORT) != 0, h);
+         if (_stretchFn && _lastStretch[live[k]].done) t.tTotalTraj *= _lastStretch[live[k]].factor; // the same path over a longer time
          if (addTorques && nCa == 0)
          {
             // (unpackOutputRows reads torque rows only beside Cartesian rows, as the output stage makes them)

@@ -1,6 +1,6 @@
 // batest_batch_main.cpp -- command-line driver of the many-path extension BA::optimizeBatch().
 //
-//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques]
+//   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]]
 //
 // --audit [tol] (builds with -DBATOTP_HAVE_AUDIT, i.e. the product's): the finished trajectories are audited against the
 // limits on the device (BA::setAuditTolerance, include/batotp_hip_audit.h; tol defaults to 0) and one summary line names
@@ -9,6 +9,10 @@
 // --torques (builds with -DBATOTP_HAVE_INVDYN, i.e. the product's): paths planned without torque limits get torque rows from the
 // inverse dynamics of the chain model along the finished samples (BA::setOutputTorques, include/batotp_hip_invdyn.h); with
 // --audit one more line per path gives the peak utilisation of the configuration's torque range.
+// --stretch [target] (builds with -DBATOTP_HAVE_STRETCH, i.e. the product's): the finished trajectories are stretched in time, each by
+// its own factor, until their velocity and acceleration peaks are within target (BA::setStretchToLimits,
+// include/batotp_hip_stretch.h; target defaults to 1) -- before --torques and --audit, which then see the stretched samples.  One
+// summary line: paths stretched, largest factor, paths not passing, paths skipped.
 // --auto-integ-res leaves BA's class default on (reference ba.h:309; the reference's own driver switches it off,
 // test/main.cpp:53): every path then integrates with the step the rule of ba.cpp:493-556 derives from it.
 // (--host-resample / --host-output are accepted and ignored: since round 4 both stages always run behind the C-ABI.)
@@ -31,7 +35,7 @@ int main(int argc, char *argv[])
 {
    if (argc < 3)
    {
-      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques]\n");
+      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]]\n");
       return 2;
    }
    const int nPaths = atoi(argv[2]);
@@ -43,6 +47,9 @@ int main(int argc, char *argv[])
 #endif
 #ifdef BATOTP_HAVE_INVDYN
    bool torques = false;
+#endif
+#ifdef BATOTP_HAVE_STRETCH
+   double stretchTarget = 0;
 #endif
    for (int k = 3; k < argc; ++k)
    {
@@ -58,6 +65,19 @@ int main(int argc, char *argv[])
          {
             const double v = strtod(argv[k + 1], &end);
             if (end != argv[k + 1] && *end == 0 && v >= 0) { auditTol = v; ++k; }
+         }
+         continue;
+      }
+#endif
+#ifdef BATOTP_HAVE_STRETCH
+      if (std::string(argv[k]) == "--stretch")
+      {
+         stretchTarget = 1;
+         char *end = nullptr;
+         if (k + 1 < argc)
+         {
+            const double v = strtod(argv[k + 1], &end);
+            if (end != argv[k + 1] && *end == 0 && v > 0 && v <= 1) { stretchTarget = v; ++k; }
          }
          continue;
       }
@@ -83,6 +103,9 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_INVDYN
    planner.setOutputTorques(torques);
 #endif
+#ifdef BATOTP_HAVE_STRETCH
+   planner.setStretchToLimits(stretchTarget);
+#endif
    if (allDevices) nDevices = planner.useAllDevices();
    else if (nDevices > 0)
    {
@@ -104,6 +127,23 @@ int main(int argc, char *argv[])
           planner.getLastOutputMs(), planner.getLastOutputKernelMs());
    if (failed < 0 || failed == nPaths) return 1;
    bool nonfinite = false;
+#ifdef BATOTP_HAVE_STRETCH
+   if (stretchTarget > 0)
+   {
+      const std::vector<BatchStretch> &st = planner.getLastStretch();
+      int nStretched = 0, nNotPassing = 0, nSkipped = 0, worst = -1;
+      for (size_t p = 0; p < st.size(); ++p)
+      {
+         if (st[p].skipped) ++nSkipped;
+         if (!st[p].done) continue;
+         if (st[p].nOut > st[p].nIn) ++nStretched;
+         if (st[p].status != 0) ++nNotPassing;
+         if (worst < 0 || st[p].factor > st[worst].factor) worst = (int)p;
+      }
+      printf("stretch (target %g): %d of %d paths stretched, largest factor %.6f (path %d), %d not passing, %d skipped\n", stretchTarget, nStretched,
+             (int)st.size(), worst < 0 ? 1.0 : st[worst].factor, worst, nNotPassing, nSkipped);
+   }
+#endif
 #ifdef BATOTP_HAVE_AUDIT
    if (auditTol >= 0)
    {
