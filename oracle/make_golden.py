@@ -10,6 +10,8 @@ For every case this script
   3. runs oracle/_build/dump_knots (host resampling of this repo, no device) to record the fp64
      knot values and the problem description that feed the hot path.
 The fixtures are DATA (inputs and expected outputs).  No reference source is copied.
+The failure pins (PIN_CASES below: failed bisections, the time limit) are a second table: pinned by the reference's log, read as a
+stream, and its float32 files; oracle/README.md has the list.
 
 Usage:  python oracle/make_golden.py [case ...]
 """
@@ -109,9 +111,9 @@ def synth_ur(seed, n_coarse, **cfg):
     return build
 
 
-def synth_cspr(seed, n_coarse, repeat_every=0, **cfg):
+def synth_cspr(seed, n_coarse, repeat_every=0, amp=3.0, **cfg):
     def build(work):
-        ca = pathgen.cspr_fine(seed, n_coarse)
+        ca = pathgen.cspr_fine(seed, n_coarse, amp=amp)
         if repeat_every:
             ca = with_repeats(ca, repeat_every)
         pathgen.write_traj_bin(os.path.join(work, "path.dat"), 0.005, None, ca)
@@ -173,7 +175,188 @@ CASES = {
 }
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Failure pins: bisections that fail (ba.cpp:1307-1319, the -1 that ba.cpp:1091 ignores) and sweeps that run into maxIntegTime
+# (ba.cpp:1117-1122), pinned by the reference's log and its float32 files.  A table of their own: these cases carry a pin.json
+# and none of the files the other case lists of tests/helpers.py are keyed on.  Cases of one family with the same config.dat
+# differ in the path only, so the device tests can run them as one ragged batch.
+
+def _raised_cosine(n, lo, hi, height):
+    """height * (1 - cos) / 2 over the fractions [lo, hi] of an n-point path, zero outside (a window may reach past an end)"""
+    x = np.arange(n, dtype=np.float64) / (n - 1)
+    w = np.zeros(n)
+    m = (x >= lo) & (x <= hi)
+    w[m] = 0.5 * height * (1.0 - np.cos(2.0 * np.pi * (x[m] - lo) / (hi - lo)))
+    return w
+
+
+GEN3_CFG = dict(n_joints=3, jnt_vel=[3, 2, 5], jnt_acc=[20, -1, 12], max_integ_time=30.0)
+
+
+def synth_gen3_windows(seed, n_coarse, windows, hover=None, **cfg):
+    """the GEN7DOF recipe with 3 joints; joint 1 -- the one with the NEGATIVE acceleration limit, for which no sddot is admissible
+    wherever it moves -- stands exactly still except in the windows (lo, hi, height): raised-cosine bumps.  hover = (amplitude,
+    periods): a ripple so small that |theta'| of that joint crosses jntThresh again and again"""
+    def build(work):
+        th = pathgen.gen7dof_fine(seed, n_coarse, n_joints=3).astype(np.float64)
+        n = th.shape[1]
+        j1 = np.zeros(n)
+        for lo, hi, height in windows:
+            j1 += _raised_cosine(n, lo, hi, height)
+        if hover:
+            j1 += hover[0] * np.sin(2.0 * np.pi * hover[1] * np.arange(n) / (n - 1))
+        th[1] = j1
+        pathgen.write_traj_bin(os.path.join(work, "path.dat"), 0.01, th.astype(np.float32), None)
+        kw = dict(robot="GENJNT", is_parallel=0, n_cart=3, traj_file="path.dat", is_bin=1, path_type="JOINT", degrees=0,
+                  jnt_acc_on=1, integ_res=0.01, theta_res=0.1, theta_res2=0.1, out_res=0.008, out_smooth=5)
+        kw.update(GEN3_CFG)
+        kw.update(cfg)
+        pathgen.write_config(os.path.join(work, "config.dat"), **kw)
+    return build
+
+
+def synth_genjnt(seed, n_coarse, n_joints, jnt_vel, jnt_acc, scale=5.0, **cfg):
+    """the GEN7DOF recipe with another joint count and one limit per joint"""
+    def build(work):
+        th = pathgen.gen7dof_fine(seed, n_coarse, n_joints=n_joints, scale=scale)
+        pathgen.write_traj_bin(os.path.join(work, "path.dat"), 0.01, th, None)
+        kw = dict(robot="GENJNT", is_parallel=0, n_joints=n_joints, n_cart=3, traj_file="path.dat", is_bin=1, path_type="JOINT",
+                  degrees=0, jnt_vel=jnt_vel, jnt_acc_on=1, jnt_acc=jnt_acc, integ_res=0.01, max_integ_time=200000.0,
+                  theta_res=0.1, theta_res2=0.1, out_res=0.008, out_smooth=5)
+        kw.update(cfg)
+        pathgen.write_config(os.path.join(work, "config.dat"), **kw)
+    return build
+
+
+_A = dict(jnt_thresh=1e-3, max_integ_time=300.0)                       # family A: every path finishes
+_C = dict(jnt_thresh=1e-3, max_integ_time=10.0)                        # family C: 1001 steps, between the sweeps of some paths
+_B = dict(max_integ_time=20.0, trq_max=[8] * 3, trq_min=[1.2] * 3)     # family B: a narrow tension band, 2001 steps
+_E = {"maxIntegTime": 6, "JntTrqMin": "NAN NAN"}
+
+# name -> (family, builder).  Cases of one family whose config.dat is the same file form one ragged batch in the device tests.
+PIN_CASES = {
+    # A. failures the path survives: joint 1 (acceleration limit -1) moves in windows only; jntThresh 1e-3 so that a window may
+    #    begin AT an end point (theta' of that joint below the threshold there: the sweep's first stage passes, the next ones
+    #    fail).  A window that has the joint moving at the end point itself fails the first stage, and such a sweep can never
+    #    finish (sdot = sddot = 0 stay): those paths are in family C, pinned as aborts.
+    "pin_a_window_mid": ("A", synth_gen3_windows(31, 12, [(0.40, 0.50, 0.3)], **_A)),
+    "pin_a_window_first": ("A", synth_gen3_windows(35, 12, [(0.0, 0.1, 0.3)], **_A)),      # first stages of the forward sweep
+    "pin_a_window_last": ("A", synth_gen3_windows(36, 12, [(0.9, 1.0, 0.3)], **_A)),       # first stages of the reverse sweep
+    "pin_a_two_windows": ("A", synth_gen3_windows(37, 12, [(0.2, 0.3, 0.3), (0.6, 0.75, -0.2)], **_A)),
+    "pin_a_hover": ("A", synth_gen3_windows(38, 12, [], hover=(3e-3, 7), **_A)),           # |theta'| crosses jntThresh repeatedly
+    "pin_a_no_window": ("A", synth_gen3_windows(39, 12, [], **_A)),
+    # B. the cable robot where the tension band does not admit the path: failures that run into the time limit
+    "pin_b_ser_rev_abort": ("B", synth_cspr(37, 10, amp=2.5, **_B)),
+    "pin_b_ser_fwd_abort": ("B", synth_cspr(39, 10, amp=4.0, **_B)),
+    "pin_b_ser_finishes": ("B", synth_cspr(38, 10, amp=2.5, **_B)),
+    "pin_b_par_rev_abort": ("B", synth_cspr(37, 10, amp=2.5, par2ser=0, **_B)),
+    "pin_b_par_finishes": ("B", synth_cspr(38, 10, amp=2.5, par2ser=0, **_B)),
+    "pin_b_par_svd_finishes": ("B", synth_cspr(38, 10, amp=2.5, par2ser=0, is_svd=1, **_B)),
+    # C. the time limit: with and without failures before it, in either sweep, beside a path that finishes
+    "pin_c_rev_late": ("C", synth_gen3_windows(36, 12, [(0.9, 1.0, 0.3)], **_C)),          # pin_a_window_last's path
+    "pin_c_fwd_late": ("C", synth_gen3_windows(35, 12, [(0.0, 0.1, 0.3)], **_C)),          # pin_a_window_first's: rev 989, fwd 1048
+    "pin_c_fwd_late_quiet": ("C", synth_gen3_windows(39, 12, [], **_C)),                   # pin_a_no_window's: rev 999, fwd 1066
+    "pin_c_first_stage_fails_fwd": ("C", synth_gen3_windows(35, 12, [(-0.03, 0.07, 0.3)], **_C)),
+    "pin_c_first_stage_fails_rev": ("C", synth_gen3_windows(36, 12, [(0.93, 1.03, 0.3)], **_C)),
+    "pin_c_finishes": ("C", synth_gen3_windows(60, 8, [(0.3, 0.45, 0.3)], **_C)),
+    "pin_c_gen7dof_rev_late": ("C", synth_gen7dof(0, 50, max_integ_time=20.0)),            # synth_gen7dof_s0's recipe, N < 3000
+    # D. joint counts and limit spread; all finish, none fails
+    "pin_d_1_joint": ("D", synth_genjnt(32, 12, 1, [5], [10])),
+    "pin_d_2_joints": ("D", synth_genjnt(40, 12, 2, [5, 3], [10, 25])),
+    "pin_d_8_joints": ("D", synth_genjnt(33, 12, 8, [5] * 8, [10] * 8)),
+    "pin_d_5_joints_decades": ("D", synth_genjnt(34, 12, 5, [0.5, 5, 50, 500, 3], [2000, 200, 20, 2, 30])),
+    # E. the shipped two-link arm with its torque limits tightened until it stalls
+    "pin_e_rr_trq_12_8": ("E", shipped("RR", dict(_E, JntTrqMax="12 8"))),
+    "pin_e_rr_trq_6_4": ("E", shipped("RR", dict(_E, JntTrqMax="6 4"))),
+}
+
+
+def run_reference_streaming(work):
+    """the reference binary on work/config.dat, its stdout read line by line: the bisection-failure messages are counted, their
+    continuation lines dropped, every other non-empty line kept.  (A stalled path prints millions of messages: never capture the log
+    whole.)  Returns (return code, failure messages, kept lines, bytes of log, seconds)"""
+    import time
+    t0 = time.time()
+    p = subprocess.Popen([LOADER, REF_BIN, "config.dat"], cwd=work, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
+    fails, kept, nbytes = 0, [], 0
+    for raw in p.stdout:
+        nbytes += len(raw)
+        if b"applyAccelConstraintsBisectionPt() error" in raw:
+            fails += 1
+        elif raw.startswith(b"  sdot was reduced to") or raw.startswith(b"  did not respect accel") or raw.startswith(b"  sdot point not found"):
+            continue
+        elif raw.strip():
+            kept.append(raw.decode("latin-1"))
+    rc = p.wait()
+    return rc, fails, "".join(kept), nbytes, time.time() - t0
+
+
+PIN_CAPS = dict(seconds=10.0, log_bytes=50e6, knots=3000, steps=40000, file_bytes=150e3)
+
+
+def pin_case(name, write=True):
+    family, build = PIN_CASES[name]
+    dst = os.path.join(GOLD, name)
+    with tempfile.TemporaryDirectory() as work:
+        build(work)
+        inputs = sorted(os.listdir(work))
+        rc, fails, log, nbytes, secs = run_reference_streaming(work)
+        assert secs < PIN_CAPS["seconds"] and nbytes < PIN_CAPS["log_bytes"], (name, secs, nbytes)
+        m_rev = re.search(r"rev\. integ\.:\s*(\d+) steps", log)
+        m_fwd = re.search(r"fwd\. integ\.:\s*(\d+) steps.*?traj time\. ([0-9.]+) sec", log)
+        n_knots = re.search(r"after splineFact: (\d+)", log)
+        late = len(re.findall(r"Error in sweep\(\): maxIntegTime", log))
+        assert late <= 1, (name, log[-2000:])
+        aborted = None if not late else ("fwd" if m_rev else "rev")
+        have_files = os.path.exists(os.path.join(work, "s-sdot.dat"))
+        assert have_files == (aborted is None) and (m_fwd is not None) == (aborted is None), (name, rc, log[-2000:])
+        assert (rc == 0) == (aborted is None), (name, rc)
+        dk = subprocess.run([DUMP, "config.dat"], cwd=work, capture_output=True, text=True)
+        if dk.returncode != 0:
+            raise RuntimeError(f"{name}: dump_knots failed\n{dk.stdout[-2000:]}")
+        kb = open(os.path.join(work, "knots.bin"), "rb").read()
+        N, nJ, nC = (int(v) for v in np.frombuffer(kb, "<i8", 3, 0))
+        sres = float(np.frombuffer(kb, "<f8", 1, 24)[0])
+        y = np.frombuffer(kb, "<f8", (nJ + nC) * N, 32).reshape(nJ + nC, N)
+        pin = {
+            "case": name, "family": family, "n_knots": N, "n_knots_ref": int(n_knots.group(1)), "n_joints": nJ, "n_cart": nC,
+            "sres_hex": float(sres).hex(),
+            "n_rev": int(m_rev.group(1)) if m_rev else None, "n_fwd": int(m_fwd.group(1)) if m_fwd else None,
+            "t_total_print": float(m_fwd.group(2)) if m_fwd else None,
+            "ref_bisect_fail_msgs": fails, "aborted": aborted, "ref_return_code": rc, "inputs": inputs,
+            "sha256_rev": None, "sha256_fwd": None, "sha256_traj_out": None,
+            "sha256_knots": hashlib.sha256(np.ascontiguousarray(y).tobytes()).hexdigest(),
+            "reference": "prebuilt /root/reference/bin/batest run in the build container",
+        }
+        assert pin["n_knots"] == pin["n_knots_ref"] <= PIN_CAPS["knots"], (name, pin)
+        assert max(pin["n_rev"] or 0, pin["n_fwd"] or 0) <= PIN_CAPS["steps"], (name, pin)
+        if aborted is None:
+            curves = pathgen.read_s_sdot(os.path.join(work, "s-sdot.dat"))
+            pin["sha256_rev"] = hashlib.sha256(curves[0][1].tobytes() + curves[0][2].tobytes()).hexdigest()
+            pin["sha256_fwd"] = hashlib.sha256(curves[1][1].tobytes() + curves[1][2].tobytes()).hexdigest()
+            pin["sha256_traj_out"] = hashlib.sha256(open(os.path.join(work, "traj_out.dat"), "rb").read()).hexdigest()
+        print(f"{name}: N={N} rev={pin['n_rev']} fwd={pin['n_fwd']} T={pin['t_total_print']} fails={fails} aborted={aborted} "
+              f"log={nbytes / 1e6:.1f} MB in {secs:.1f} s")
+        if not write:
+            return pin
+        shutil.rmtree(dst, ignore_errors=True)
+        os.makedirs(dst)
+        for f in inputs:
+            shutil.copy(os.path.join(work, f), os.path.join(dst, f))
+            os.chmod(os.path.join(dst, f), 0o644)
+        if aborted is None:
+            shutil.copy(os.path.join(work, "s-sdot.dat"), os.path.join(dst, "ref_s-sdot.dat"))
+        with open(os.path.join(dst, "pin.json"), "w") as f:
+            json.dump(pin, f, indent=1)
+            f.write("\n")
+        for f in os.listdir(dst):
+            assert os.path.getsize(os.path.join(dst, f)) <= PIN_CAPS["file_bytes"], (name, f)
+    return pin
+
+
 def run_case(name):
+    if name in PIN_CASES:
+        return pin_case(name)
     build, full = CASES[name]
     dst = os.path.join(GOLD, name)
     shutil.rmtree(dst, ignore_errors=True)
@@ -228,6 +411,8 @@ def run_case(name):
 
 
 if __name__ == "__main__":
-    names = sys.argv[1:] or list(CASES)
+    names = sys.argv[1:] or list(CASES) + list(PIN_CASES)
     for n in names:
         run_case(n)
+    pins = [os.path.join(GOLD, n, f) for n in PIN_CASES if os.path.isdir(os.path.join(GOLD, n)) for f in os.listdir(os.path.join(GOLD, n))]
+    assert sum(os.path.getsize(f) for f in pins) < 1e6, "the failure pins together must stay under 1 MB"

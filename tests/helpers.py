@@ -30,6 +30,9 @@ RESAMPLE_CASES = sorted(d for d in os.listdir(GOLD) if os.path.exists(os.path.jo
 
 OUTPUT_CASES = sorted(d for d in os.listdir(GOLD) if os.path.exists(os.path.join(GOLD, d, "output.npz")))
 
+# failure pins (oracle/make_golden.py: PIN_CASES): failed bisections and the time limit, pinned by the reference's log and float32 files
+PIN_CASES = sorted(d for d in os.listdir(GOLD) if os.path.exists(os.path.join(GOLD, d, "pin.json")))
+
 # how the digest-only inputs are regenerated (must match oracle/make_golden.py)
 DIGEST_INPUTS = {
     "synth_gen7dof_s4_50k": lambda: (pathgen.gen7dof_fine(4, 871), None, 0.01),
@@ -86,6 +89,117 @@ class Case:
 
     def max_steps(self):
         return int(max(self.expected["n_rev"], self.expected["n_fwd"]) + 64)
+
+
+class PinCase(Case):
+    """a failure pin: config.dat and the committed input path, resampled by the host library against the oracle shim like the
+    digest-only cases; pin.json holds what the reference's log and float32 files pin (expected["aborted"]: None, "rev" or "fwd")"""
+
+    def __init__(self, name):
+        self.name = name
+        self.dir = os.path.join(GOLD, name)
+        self.expected = json.load(open(os.path.join(self.dir, "pin.json")))
+        self.full = False
+        self.config = open(os.path.join(self.dir, "config.dat")).read()
+        with tempfile.TemporaryDirectory() as work:
+            for f in self.expected["inputs"]:
+                with open(os.path.join(self.dir, f), "rb") as src, open(os.path.join(work, f), "wb") as dst:
+                    dst.write(src.read())
+            r = subprocess.run([os.path.join(BUILD, "dump_knots"), "config.dat"], cwd=work, capture_output=True, text=True)
+            assert r.returncode == 0, r.stdout[-2000:]
+            kb = open(os.path.join(work, "knots.bin"), "rb").read()
+            N, nJ, nC = (int(v) for v in np.frombuffer(kb, "<i8", 3, 0))
+            self.sres = float(np.frombuffer(kb, "<f8", 1, 24)[0])
+            self.y = np.frombuffer(kb, "<f8", (nJ + nC) * N, 32).reshape(nJ + nC, N).copy()
+            self.problem = problem_from_bytes(np.frombuffer(open(os.path.join(work, "problem.bin"), "rb").read(), np.uint8))
+        if self.problem.robot_type in (capi.ROBOT_KUKA, capi.ROBOT_RR):
+            self.problem.flags |= capi.F_HOST_TRIG     # as BA::fillProblem sets it (see Case)
+        f = os.path.join(self.dir, "ref_s-sdot.dat")
+        self.ref = pathgen.read_s_sdot(f) if os.path.exists(f) else None
+        self.aborted = self.expected["aborted"]
+        assert (self.ref is None) == (self.aborted is not None)
+
+    def max_steps(self):
+        """room for the sweeps that finish; for an aborted case room for the steps the time limit allows (ba.cpp:984, :1117)"""
+        if self.aborted is None:
+            return int(max(self.expected["n_rev"], self.expected["n_fwd"]) + 64)
+        return int(np.floor(self.problem.max_integ_time / self.problem.integ_res)) + 2 + 64
+
+
+_PIN_CACHE = {}
+
+
+def pin_case(name):
+    """PinCase(name), resampled once per session"""
+    if name not in _PIN_CACHE:
+        _PIN_CACHE[name] = PinCase(name)
+    return _PIN_CACHE[name]
+
+
+def pin_batches(family):
+    """the pins of a family grouped by config.dat: the paths of one group share a problem description, i.e. can run as one batch"""
+    groups = {}
+    for name in PIN_CASES:
+        c = pin_case(name)
+        if c.expected["family"] == family:
+            groups.setdefault(c.config, []).append(c)
+    return list(groups.values())
+
+
+ST_ABORT = capi.ST_MAX_INTEG_TIME | capi.ST_CAPACITY | capi.ST_NONFINITE
+
+
+def run_pin_batch(ctx, cases, extra_flags=0):
+    """knots -> precompute -> both sweeps of the cases as one batch: a list of dicts "result", "rev", "fwd" (a curve is None
+    where its sweep did not finish)"""
+    prob = cases[0].problem
+    if extra_flags:
+        prob = capi.Problem.from_buffer_copy(bytes(prob))
+        prob.flags |= extra_flags
+    b = capi.Batch(ctx, prob, [c.n for c in cases], max(c.max_steps() for c in cases))
+    for k, c in enumerate(cases):
+        b.upload_knots(k, [c.y], [c.sres])
+    precompute_with_trig(ctx, b, prob, len(cases))
+    b.sweep(-1); b.sweep(+1)
+    res = b.results()
+    out = []
+    for k in range(len(cases)):
+        d = {"result": res[k].copy()}
+        d["rev"] = b.curve(k, -1) if not (int(res[k]["status_rev"]) & ST_ABORT) else None
+        d["fwd"] = b.curve(k, +1) if not (int(res[k]["status_fwd"]) & ST_ABORT) else None
+        out.append(d)
+    b.close()
+    return out
+
+
+def assert_matches_pin(case, out):
+    """what the reference binary pinned for a failure pin (its log; its float32 files where it wrote them) against one path's rows
+    and curves.  An aborted run of the reference prints no step count for the sweep it gave up and runs no forward sweep after
+    a reverse sweep that gave up: for those only the time-limit bit and the failure messages up to the abort are pinned"""
+    e, r = case.expected, out["result"]
+    st_rev, st_fwd = int(r["status_rev"]), int(r["status_fwd"])
+    fails = int(r["n_bisect_fail_rev"]) + int(r["n_bisect_fail_fwd"])
+    what = (case.name, {f: r[f].item() for f in r.dtype.names}, e)
+    assert fails == e["ref_bisect_fail_msgs"], what
+    assert bool((st_rev | st_fwd) & capi.ST_BISECT_FAIL) == (fails > 0), what
+    if case.aborted is None:
+        assert int(r["n_rev"]) == e["n_rev"] and int(r["n_fwd"]) == e["n_fwd"], what
+        assert abs(float(r["t_total"]) - e["t_total_print"]) < 5.1e-4, what   # the log prints three decimals
+        assert not ((st_rev | st_fwd) & ST_ABORT), what
+        assert f32_digest(*out["rev"]) == e["sha256_rev"], case.name
+        assert f32_digest(*out["fwd"]) == e["sha256_fwd"], case.name
+        for which, (sres, s, sd), (ms, msd) in zip(("reverse", "forward"), case.ref, (out["rev"], out["fwd"])):
+            assert_bit_equal(ms.astype(np.float32), s, f"{case.name}: {which} s against the reference's s-sdot.dat")
+            assert_bit_equal(msd.astype(np.float32), sd, f"{case.name}: {which} sdot against the reference's s-sdot.dat")
+    elif case.aborted == "rev":
+        assert st_rev & capi.ST_MAX_INTEG_TIME and not (st_rev & (capi.ST_CAPACITY | capi.ST_NONFINITE)), what
+        # the reference stops here.  The product runs no forward sweep either: no step, no point, no failure of its own (its
+        # status word repeats the reverse sweep's, a convention of the product the log cannot show)
+        assert int(r["n_rev"]) == 0 and int(r["n_fwd"]) == 0 and int(r["steps_fwd"]) == 0 and int(r["n_bisect_fail_fwd"]) == 0, what
+    else:
+        assert not (st_rev & ST_ABORT) and int(r["n_rev"]) == e["n_rev"], what
+        assert st_fwd & capi.ST_MAX_INTEG_TIME and not (st_fwd & (capi.ST_CAPACITY | capi.ST_NONFINITE)), what
+        assert int(r["n_fwd"]) == 0, what
 
 
 class PrefixCase:
