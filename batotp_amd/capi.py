@@ -227,6 +227,20 @@ STRETCH_DTYPE = np.dtype([("n_in", "<i8"), ("n_out", "<i8"), ("factor", "<f8"), 
 assert STRETCH_DTYPE.itemsize == C.sizeof(PathStretch) == 32
 
 
+# ---- stretching until the torque limits pass (include/batotp_hip_tscale.h) ------------------------------------------------
+TSCALE_BLOCK_POINTS = 128           # BATOTP_TSCALE_BLOCK_POINTS: points per workgroup of the scale kernel
+STRETCH_STATIC = 3                  # BATOTP_STRETCH_STATIC
+
+
+class PathTscale(C.Structure):
+    """struct batotp_path_tscale"""
+    _fields_ = [("s", C.c_double), ("at", C.c_int64), ("row", C.c_int32), ("side", C.c_int32), ("n_static", C.c_int64), ("reserved", C.c_int64)]
+
+
+TSCALE_DTYPE = np.dtype([("s", "<f8"), ("at", "<i8"), ("row", "<i4"), ("side", "<i4"), ("n_static", "<i8"), ("reserved", "<i8")])
+assert TSCALE_DTYPE.itemsize == C.sizeof(PathTscale) == 40
+
+
 def _dptr(a: Optional[np.ndarray]):
     if a is None:
         return None
@@ -388,6 +402,26 @@ class Library:
                 fn = getattr(L, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
+
+        # ... and of include/batotp_hip_tscale.h (stretched until the torque limits pass), likewise
+        tscale_sig = {
+            "batotp_hip_output_torque_scale": [P, C.POINTER(Problem), C.POINTER(SerialModel), C.c_uint32, C.c_double, C.POINTER(P), C.c_void_p],
+            "batotp_hip_output_stretch_torques": [P, C.POINTER(Problem), C.POINTER(SerialModel), C.c_uint32, C.c_double, I32, C.c_double,
+                                                  C.POINTER(P), C.c_void_p, C.c_void_p],
+            "batotp_hip_output_tscale_ms": [P, C.POINTER(C.c_float)],
+            "batotp_hip_output_tscale_ranges": [P, C.POINTER(I32)],
+        }
+        self.tscale_symbols = sorted(tscale_sig)
+        self.has_tscale = all(hasattr(L, name) for name in tscale_sig)
+        if self.has_tscale:
+            for name, argtypes in tscale_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_tscale(self):
+        if not self.has_tscale:
+            raise BatotpError(f"{self.path} does not export the torque-scale entry points (include/batotp_hip_tscale.h)")
 
     def need_stretch(self):
         if not self.has_stretch:
@@ -763,6 +797,50 @@ class Output:
         self.L.need_stretch()
         v = C.c_int32(0)
         self.L.check(self.lib.batotp_hip_output_stretch_ranges(self.handle, C.byref(v)), "output_stretch_ranges")
+        return int(v.value)
+
+    def torque_scale(self, prob: Problem, model: SerialModel, target: float = 1.0, host_trig: bool = True, flags: Optional[int] = None):
+        """(a NEW Output, records): the rows of Output.torques(model) and one TSCALE_DTYPE row per path -- the largest speed factor
+        the torque range of prob admits at target, where it binds, and the points at which gravity alone leaves the range
+        (batotp_hip_output_torque_scale, include/batotp_hip_tscale.h); flags overrides host_trig with a raw flag word"""
+        self.L.need_tscale()
+        new = self._like()
+        rec = np.zeros(self.n_paths, dtype=TSCALE_DTYPE)
+        f = (F_HOST_TRIG if host_trig else 0) if flags is None else int(flags)
+        self.L.check(self.lib.batotp_hip_output_torque_scale(self.handle, C.byref(prob), C.byref(model), f, float(target), C.byref(new.handle),
+                                                             rec.ctypes.data_as(C.c_void_p)), "batotp_hip_output_torque_scale")
+        new._read_info()
+        return new, rec
+
+    def stretch_torques(self, prob: Problem, model: SerialModel, target: float = 1.0, max_rounds: int = 8, max_factor: float = 16.0,
+                        host_trig: bool = True, flags: Optional[int] = None):
+        """(a NEW Output, report, records): every path stretched, each by its own factor, until its velocity, acceleration AND torque
+        peaks are <= target (batotp_hip_output_stretch_torques); the Output carries the torque rows of the stretched paths, report is
+        one STRETCH_DTYPE row per path (status STRETCH_STATIC: gravity alone exceeds the range), records the TSCALE_DTYPE rows of
+        the result"""
+        self.L.need_tscale()
+        new = self._like()
+        report = np.zeros(self.n_paths, dtype=STRETCH_DTYPE)
+        rec = np.zeros(self.n_paths, dtype=TSCALE_DTYPE)
+        f = (F_HOST_TRIG if host_trig else 0) if flags is None else int(flags)
+        self.L.check(self.lib.batotp_hip_output_stretch_torques(self.handle, C.byref(prob), C.byref(model), f, float(target), int(max_rounds),
+                                                                float(max_factor), C.byref(new.handle), report.ctypes.data_as(C.c_void_p),
+                                                                rec.ctypes.data_as(C.c_void_p)), "batotp_hip_output_stretch_torques")
+        new._read_info()
+        return new, report, rec
+
+    def tscale_ms(self) -> float:
+        """milliseconds of the scale kernels of the call that made this Output (torque_scale / stretch_torques), all rounds"""
+        self.L.need_tscale()
+        v = C.c_float(0)
+        self.L.check(self.lib.batotp_hip_output_tscale_ms(self.handle, C.byref(v)), "output_tscale_ms")
+        return float(v.value)
+
+    def tscale_ranges(self) -> int:
+        """launches of the scale kernel (ranges of paths, over all rounds) of the call that made this Output"""
+        self.L.need_tscale()
+        v = C.c_int32(0)
+        self.L.check(self.lib.batotp_hip_output_tscale_ranges(self.handle, C.byref(v)), "output_tscale_ranges")
         return int(v.value)
 
     def close(self):

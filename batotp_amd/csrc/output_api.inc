@@ -22,6 +22,9 @@ struct batotp_output
    bool fromStretch = false;    // made by batotp_hip_output_stretch_to / _by / _audit (stretch_api.inc) ...
    float stretchMs = 0.f;       // ... stretch kernels of that call, all rounds and ranges
    int stretchRanges = 0;       // ... and how many launches that was
+   bool fromTscale = false;     // made by batotp_hip_output_torque_scale / _stretch_torques (tscale_api.inc) ...
+   float tscaleMs = 0.f;        // ... kernels of tscale.hip.h in that call, all rounds and ranges
+   int tscaleRanges = 0;        // ... and how many launches of k_tscale that was
 };
 
 extern "C" int batotp_hip_output_destroy(batotp_output *o)

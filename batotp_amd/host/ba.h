@@ -150,7 +150,8 @@ struct BatchStretch
    long long nIn = 0, nOut = 0; // points before and after
    double factor = 1.;          // (nOut - 1) / (nIn - 1): the duration grew by this
    int rounds = 0;              // how many times the path was stretched
-   int status = 0;              // 0 passes, 1 rounds exhausted, 2 stopped at the largest factor allowed
+   int status = 0;              // 0 passes, 1 rounds exhausted, 2 stopped at the largest factor allowed, 3 (setStretchToTorqueLimits
+                                // only) gravity alone leaves the torque range somewhere on the path: no stretch helps
    bool done = false;           // false: the path failed before the output stage, or was skipped
    bool skipped = false;        // the path carries the output stage's own torque rows and was left as it is
 };
@@ -231,7 +232,17 @@ public:
    // and its paths are reported as skipped.  target <= 0 switches it off (default: nothing changes).  Defined in
    // ba_stretch.cpp, the only file of the library that refers to the entry points of that header.
    void setStretchToLimits(double target, int maxRounds = 8, double maxFactor = 16.);
-   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: stretch off)
+   // Extension: stretch the finished trajectories until their TORQUE limits pass too (include/batotp_hip_tscale.h): as
+   // setStretchToLimits, with the torque family of the audit on top -- every round makes the torque rows of the chain model along
+   // the stretched samples and the speed factor the configuration's jntTrqMax / jntTrqMin admit, and a path over its range is
+   // stretched by what that factor asks.  Where it applies -- a serial robot whose torque constraint is off, with a chain model
+   // (setSerialModel, or the built-in KUKA table) and a finite positive torque range in the configuration -- it REPLACES the
+   // stretch step and the torque step of a range: Traj::trq, nPts, tTotalTraj, getLastStretch() and the audit follow from its
+   // result as they do from those two.  Elsewhere setStretchToLimits / setOutputTorques act as they are set.  target <= 0
+   // switches it off (default: nothing changes).  Defined in ba_tscale.cpp, the only file of the library that refers to the
+   // entry points of that header.
+   void setStretchToTorqueLimits(double target, int maxRounds = 8, double maxFactor = 16.);
+   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: both stretches off)
    const std::vector<BatchStretch> &getLastStretch() const { return _lastStretch; }
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
@@ -419,6 +430,11 @@ private:
    int (*_stretchFn)(void *output, const void *problem, double target, int maxRounds, double maxFactor, size_t n, void **out,
                      BatchStretch *report) = nullptr;
    std::vector<BatchStretch> _lastStretch;
+   // batotp_hip_output_stretch_torques behind a pointer; set by setStretchToTorqueLimits (ba_tscale.cpp)
+   double _tscaleTarget = 0, _tscaleMaxFactor = 16.;
+   int _tscaleRounds = 8;
+   int (*_tscaleFn)(void *output, const void *problem, const void *model, unsigned int flags, double target, int maxRounds, double maxFactor, size_t n,
+                    void **out, BatchStretch *report) = nullptr;
    // batotp_hip_resample_chain / batotp_hip_set_kin_chain behind pointers; set by setToolPoint (ba_kin.cpp)
    int (*_kinResampleFn)(void *ctx, const void *params, const void *chain, int nPaths, const int64_t *nIn, const double *x, const double *sresIn,
                          void **out) = nullptr;

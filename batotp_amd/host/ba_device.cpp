@@ -856,7 +856,7 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
          for (size_t q = 0; q < worker[d]._lastAudit.size() && lo[d] + q < lo[d + 1]; ++q) _lastAudit[lo[d] + q] = worker[d]._lastAudit[q];
    }
    _lastStretch.clear();
-   if (_stretchFn)
+   if (_stretchFn || _tscaleFn)
    {
       _lastStretch.assign(trajs.size(), BatchStretch());
       for (size_t d = 0; d < nDev; ++d)
@@ -978,7 +978,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
    _lastAudit.clear();
    if (_auditFn) _lastAudit.assign(trajs.size(), BatchAudit()); // (setAuditTolerance; a path that fails early keeps audited = false)
    _lastStretch.clear();
-   if (_stretchFn) _lastStretch.assign(trajs.size(), BatchStretch()); // (setStretchToLimits; likewise done = false)
+   if (_stretchFn || _tscaleFn) _lastStretch.assign(trajs.size(), BatchStretch()); // (setStretchToLimits, setStretchToTorqueLimits; likewise done = false)
    if (trajs.empty()) return 0;
    if (_isInterpOnly || _sWeights[1] + _sWeights[2] < 1e-8)
    {
@@ -991,6 +991,13 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
    {
       printf("optimizeBatch(): torque rows were asked for (setOutputTorques) but there is no dynamics model for robotType=%s.\n", _robotTypeStr.c_str());
       return -1;
+   }
+   // stretched until the torque limits pass (setStretchToTorqueLimits): where torque rows would be added, with a model and a range
+   bool stretchTorques = _tscaleFn && !_isTrqConOn && !_isParallelMechOrig && myRobot.serialModel();
+   for (unsigned int j = 0; stretchTorques && j < _nJoints; ++j)
+   {
+      const double hi = j < _JntTrqMax.size() ? _JntTrqMax[j] : 0.0, lo = j < _JntTrqMin.size() ? _JntTrqMin[j] : 0.0;
+      stretchTorques = std::isfinite(hi) && std::isfinite(lo) && (hi - lo) * 0.5 > 0.0;
    }
    if (gpuAcquire() != 0) return -1;
 
@@ -1293,7 +1300,22 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       }
       if (rc) return fail("output", rc);
       ++outputCalls;
-      if (_stretchFn)
+      if (stretchTorques)
+      {
+         // the range's paths dilated in time until their audit passes WITH the torque family, and the torque rows of the result
+         // (include/batotp_hip_tscale.h): in place of the two steps below
+         float msStage = 0;
+         batotp_hip_output_ms(og.o, &msStage); // timing only (the stretched output is not the stage's)
+         kernelMs += msStage;
+         std::vector<BatchStretch> report(cnt);
+         void *stretched = nullptr;
+         rc = _tscaleFn(og.o, &prob, myRobot.serialModel(), BATOTP_F_HOST_TRIG, _tscaleTarget, _tscaleRounds, _tscaleMaxFactor, cnt, &stretched, report.data());
+         if (rc) return fail("output_stretch_torques", rc);
+         batotp_hip_output_destroy(og.o);
+         og.o = static_cast<batotp_output *>(stretched);
+         for (size_t q = 0; q < cnt; ++q) _lastStretch[live[k0 + q]] = report[q];
+      }
+      if (_stretchFn && !stretchTorques)
       {
          // the range's paths dilated in time until their audit passes, while they are in device memory: the torque rows, the
          // audit and the Traj arrays below take the stretched rows.  Torques are no function of the path alone, so a range
@@ -1317,7 +1339,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
             for (size_t q = 0; q < cnt; ++q) _lastStretch[live[k0 + q]] = report[q];
          }
       }
-      if (addTorques)
+      if (addTorques && !stretchTorques)
       {
          // the range's rows with the torques of the chain model appended, while they are in device memory (host trig tables:
          // the bits of the definition, include/batotp_hip_invdyn.h)
@@ -1348,7 +1370,7 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          // the trajectories of the range against the limits, while they are still in device memory
          std::vector<BatchAudit> audit(cnt);
          batotp_problem probAudit = prob;
-         if (addTorques)
+         if (addTorques || stretchTorques)
          {
             // the torque rows against the configuration's jntTrqMax / jntTrqMin (a configuration without a torque range keeps
             // the family off: the audit refuses a range that is not finite and positive)
@@ -1377,8 +1399,8 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          if (n == 0) { ok[live[k]] = 0; continue; }
          _nCart = (rsp.path_type == BATOTP_PATH_BOTH && nCartTaught == 6) ? 7 : nCartTaught;
          unpackOutputRows(t, flatAll.data() + at, n, nTh, nCa, nTq, sresOut[q], r.n_fwd, r.t_total, (r.status_fwd & BATOTP_ST_SHORT) != 0, h);
-         if (_stretchFn && _lastStretch[live[k]].done) t.tTotalTraj *= _lastStretch[live[k]].factor; // the same path over a longer time
-         if (addTorques && nCa == 0)
+         if ((_stretchFn || stretchTorques) && _lastStretch[live[k]].done) t.tTotalTraj *= _lastStretch[live[k]].factor; // the same path over a longer time
+         if ((addTorques || stretchTorques) && nCa == 0)
          {
             // (unpackOutputRows reads torque rows only beside Cartesian rows, as the output stage makes them)
             const double *trqRows = flatAll.data() + at + (size_t)nTh * (size_t)n;

@@ -1,6 +1,7 @@
 // batest_batch_main.cpp -- command-line driver of the many-path extension BA::optimizeBatch().
 //
 //   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]]
+//                [--stretch-torques [target]]
 //
 // --audit [tol] (builds with -DBATOTP_HAVE_AUDIT, i.e. the product's): the finished trajectories are audited against the
 // limits on the device (BA::setAuditTolerance, include/batotp_hip_audit.h; tol defaults to 0) and one summary line names
@@ -13,6 +14,11 @@
 // its own factor, until their velocity and acceleration peaks are within target (BA::setStretchToLimits,
 // include/batotp_hip_stretch.h; target defaults to 1) -- before --torques and --audit, which then see the stretched samples.  One
 // summary line: paths stretched, largest factor, paths not passing, paths skipped.
+// --stretch-torques [target] (builds with -DBATOTP_HAVE_TSCALE, i.e. the product's): the finished trajectories are stretched until
+// the torques of the chain model along them are within target of the configuration's torque range too
+// (BA::setStretchToTorqueLimits, include/batotp_hip_tscale.h; target defaults to 1), and carry those torque rows.  One summary
+// line: paths stretched, largest factor, paths not passing, of those the paths no stretch can help; with --audit one more line per
+// path gives the peak utilisation of the torque range.
 // --auto-integ-res leaves BA's class default on (reference ba.h:309; the reference's own driver switches it off,
 // test/main.cpp:53): every path then integrates with the step the rule of ba.cpp:493-556 derives from it.
 // (--host-resample / --host-output are accepted and ignored: since round 4 both stages always run behind the C-ABI.)
@@ -35,7 +41,7 @@ int main(int argc, char *argv[])
 {
    if (argc < 3)
    {
-      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]]\n");
+      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]] [--stretch-torques [target]]\n");
       return 2;
    }
    const int nPaths = atoi(argv[2]);
@@ -51,8 +57,24 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_STRETCH
    double stretchTarget = 0;
 #endif
+#ifdef BATOTP_HAVE_TSCALE
+   double tscaleTarget = 0;
+#endif
    for (int k = 3; k < argc; ++k)
    {
+#ifdef BATOTP_HAVE_TSCALE
+      if (std::string(argv[k]) == "--stretch-torques")
+      {
+         tscaleTarget = 1;
+         char *end = nullptr;
+         if (k + 1 < argc)
+         {
+            const double v = strtod(argv[k + 1], &end);
+            if (end != argv[k + 1] && *end == 0 && v > 0 && v <= 1) { tscaleTarget = v; ++k; }
+         }
+         continue;
+      }
+#endif
 #ifdef BATOTP_HAVE_INVDYN
       if (std::string(argv[k]) == "--torques") torques = true;
 #endif
@@ -106,6 +128,9 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_STRETCH
    planner.setStretchToLimits(stretchTarget);
 #endif
+#ifdef BATOTP_HAVE_TSCALE
+   planner.setStretchToTorqueLimits(tscaleTarget);
+#endif
    if (allDevices) nDevices = planner.useAllDevices();
    else if (nDevices > 0)
    {
@@ -144,6 +169,26 @@ int main(int argc, char *argv[])
              (int)st.size(), worst < 0 ? 1.0 : st[worst].factor, worst, nNotPassing, nSkipped);
    }
 #endif
+#ifdef BATOTP_HAVE_TSCALE
+   if (tscaleTarget > 0)
+   {
+      const std::vector<BatchStretch> &st = planner.getLastStretch();
+      int nDone = 0, nStretched = 0, nNotPassing = 0, nStatic = 0, worst = -1;
+      for (size_t p = 0; p < st.size(); ++p)
+      {
+         if (!st[p].done) continue;
+         ++nDone;
+         if (st[p].nOut > st[p].nIn) ++nStretched;
+         if (st[p].status != 0) ++nNotPassing;
+         if (st[p].status == 3) ++nStatic;
+         if (worst < 0 || st[p].factor > st[worst].factor) worst = (int)p;
+      }
+      if (nDone == 0) printf("stretch-torques (target %g): not applied (it needs a serial robot planned without torque limits, a chain model and a torque range)\n", tscaleTarget);
+      else
+         printf("stretch-torques (target %g): %d of %d paths stretched, largest factor %.6f (path %d), %d not passing, %d of them static\n", tscaleTarget,
+                nStretched, (int)st.size(), st[worst].factor, worst, nNotPassing, nStatic);
+   }
+#endif
 #ifdef BATOTP_HAVE_AUDIT
    if (auditTol >= 0)
    {
@@ -168,7 +213,11 @@ int main(int argc, char *argv[])
       printf(nOverPaths ? "\n" : " none\n");
       if (nonfinite) printf("audit: a trajectory holds values that are not finite\n");
 #ifdef BATOTP_HAVE_INVDYN
-      if (torques)
+      bool trqLines = torques;
+#ifdef BATOTP_HAVE_TSCALE
+      trqLines = trqLines || tscaleTarget > 0;
+#endif
+      if (trqLines)
          for (size_t p = 0; p < audit.size(); ++p)
          {
             if (!audit[p].audited) printf("torques: path %d not audited\n", (int)p);

@@ -1,0 +1,227 @@
+"""The definition of the torque scale of finished trajectories (include/batotp_hip_tscale.h) restated in numpy, driven by the pieces
+that are already pinned: the differences, the trig and the two passes of the recursion of tests/invdyn_reference.py (the oracle's
+exported bo_rnea), the cubic of tests/stretch_reference.py and the audit of tests/audit_reference.py.
+
+binary64 throughout; numpy's element-wise `/` and sqrt are the IEEE ones, every step is one operation in the stated order."""
+import math
+
+import numpy as np
+
+import invdyn_reference as ir
+import stretch_reference as sr
+from audit_reference import audit_path
+from batotp_amd import capi
+
+
+def pieces(oracle_lib, model, x, h):
+    """(A, B, G)[n_links][n] of one path with joint rows x[n_links][n] and time step h: t2, fv * qd, t4 of the torque definition"""
+    x = np.asarray(x, dtype=np.float64)
+    nl, n = model.n_links, x.shape[1]
+    assert x.shape[0] == nl
+    unit = np.float64(ir.DEG2RAD if model.degrees else 1.0)
+    v, a = ir.differences(x, h)
+    with np.errstate(all="ignore"):
+        q, qd, qdd = unit * x, unit * v, unit * a
+    fv = np.array([model.link[j].fv for j in range(nl)])
+    z, zero3 = np.zeros(nl), np.zeros(3)
+    g0 = np.array([-model.gravity[0], -model.gravity[1], -model.gravity[2]])
+    A, G = np.empty((nl, n)), np.empty((nl, n))
+    for i in range(n):
+        cq = np.array([math.cos(float(u)) for u in q[:, i]])
+        sq = np.array([math.sin(float(u)) for u in q[:, i]])
+        A[:, i] = ir._rnea(oracle_lib, model, cq, sq, np.ascontiguousarray(qd[:, i]), np.ascontiguousarray(qdd[:, i]), zero3)
+        G[:, i] = ir._rnea(oracle_lib, model, cq, sq, z, z, g0)
+    with np.errstate(all="ignore"):
+        B = fv[:, None] * qd
+    return A, B, G
+
+
+def bounds(prob, nl, target):
+    """(hi, lo)[n_links]: mid and half as the audit forms them"""
+    tmax = np.array([np.float64(prob.jnt_trq_max[j]) for j in range(nl)])
+    tmin = np.array([np.float64(prob.jnt_trq_min[j]) for j in range(nl)])
+    mid = (tmax + tmin) * 0.5
+    half = (tmax - tmin) * 0.5
+    t = np.float64(target)
+    return mid + t * half, mid - t * half
+
+
+def roots(a, b, c):
+    """(x, exists) of the candidates of a x^2 + b x + c, c < 0, element-wise"""
+    with np.errstate(all="ignore"):
+        disc = b * b - (4.0 * a) * c
+        q = b + np.sqrt(disc)
+        x = (2.0 * (-c)) / q
+        exists = (disc >= 0.0) & (q > 0.0) & np.isfinite(q) & np.isfinite(x)
+    return x, exists
+
+
+def scale_record(A, B, G, hi, lo):
+    """one capi.TSCALE_DTYPE record from the pieces of a path"""
+    rec = np.zeros((), dtype=capi.TSCALE_DTYPE)
+    rec["s"], rec["at"], rec["row"], rec["side"] = np.inf, -1, -1, 0
+    nl, n = G.shape
+    if n == 0:
+        return rec
+    with np.errstate(all="ignore"):
+        cu, cl = G - hi[:, None], lo[:, None] - G
+        inside = (cu < 0.0) & (cl < 0.0)
+    static = ~inside.all(axis=0)
+    rec["n_static"] = int(np.count_nonzero(static))
+    xu, eu = roots(A, B, cu)
+    xl, el = roots(-A, -B, cl)
+    # [point][joint][side, upper first]: the first minimum in this order is the tie rule
+    X = np.stack([xu.T, xl.T], axis=2)
+    E = np.stack([eu.T, el.T], axis=2) & ~static[:, None, None]
+    if not E.any():
+        return rec
+    m = X[E].min()
+    at, row, side = (int(v) for v in np.argwhere(E & (X == m))[0])
+    rec["s"], rec["at"], rec["row"], rec["side"] = m, at, row, (1, -1)[side]
+    return rec
+
+
+def path_with_torques(oracle_lib, model, rows, h, hi, lo):
+    """(rows with n_links torque rows appended, record) of one path rows[n_links + n_cart][n]"""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    nl = model.n_links
+    A, B, G = pieces(oracle_lib, model, rows[:nl], h)
+    with np.errstate(all="ignore"):
+        tau = (A + B) + G
+    return np.concatenate([rows, tau]), scale_record(A, B, G, hi, lo)
+
+
+def torque_scale(oracle_lib, model, rows_list, sres, prob, target=1.0):
+    """batotp_hip_output_torque_scale: (rows with torques of every path, capi.TSCALE_DTYPE records)"""
+    K = len(rows_list)
+    sres = np.broadcast_to(np.asarray(sres, dtype=np.float64), (K,))
+    hi, lo = bounds(prob, model.n_links, target)
+    out, rec = [], np.zeros(K, dtype=capi.TSCALE_DTYPE)
+    for k, r in enumerate(rows_list):
+        w, rec[k] = path_with_torques(oracle_lib, model, r, sres[k], hi, lo)
+        out.append(w)
+    return out, rec
+
+
+def with_trq_on(prob):
+    p = capi.Problem.from_buffer_copy(bytes(prob))
+    p.flags |= capi.F_TRQ_ON
+    return p
+
+
+def stretch_torques(oracle_lib, model, rows_list, sres, n_cart, prob, target=1.0, max_rounds=8, max_factor=16.0, cache=None):
+    """the rounds of batotp_hip_output_stretch_torques: (rows with torques of every path, report as capi.STRETCH_DTYPE, final audit,
+    records as capi.TSCALE_DTYPE).  cache: a dict shared by calls on the SAME rows, model, limits and target -- what a path of a
+    given point count gives does not depend on the other arguments"""
+    K = len(rows_list)
+    nl = model.n_links
+    sres = np.broadcast_to(np.asarray(sres, dtype=np.float64), (K,))
+    src = [np.ascontiguousarray(r, dtype=np.float64) for r in rows_list]
+    n_in = [r.shape[1] for r in src]
+    hi, lo = bounds(prob, nl, target)
+    probT = with_trq_on(prob)
+    cache = {} if cache is None else cache
+
+    def evaluate(k, n2):
+        if (k, n2) not in cache:
+            w, rec = path_with_torques(oracle_lib, model, sr.stretch_rows(src[k], n2), sres[k], hi, lo)
+            cache[(k, n2)] = (w, rec, audit_path(w, sres[k], nl, n_cart, nl, probT, 0.0))
+        return cache[(k, n2)]
+
+    n2, rounds, status, capped = list(n_in), [0] * K, [capi.STRETCH_PASSES] * K, [False] * K
+    while True:
+        again = False
+        for k in range(K):
+            _, rec, aud = evaluate(k, n2[k])
+            kin_ok, need = sr.path_passes(aud, target)
+            ok = kin_ok
+            trq_ok = float(aud["fam"][capi.AUDIT_TRQ]["peak"]) <= target
+            if not trq_ok:
+                ok = False
+                if int(rec["n_static"]) == 0 and float(rec["s"]) < 1.0:
+                    need = max(need, 1.0 / float(rec["s"]))
+            if ok:
+                status[k] = capi.STRETCH_PASSES
+                continue
+            if not trq_ok and int(rec["n_static"]) > 0 and kin_ok:
+                status[k] = capi.STRETCH_STATIC
+                continue
+            if capped[k]:
+                status[k] = capi.STRETCH_CAPPED
+                continue
+            if rounds[k] >= max_rounds:
+                status[k] = capi.STRETCH_ROUNDS
+                continue
+            m = n2[k] - 1
+            want = float(m) * need
+            intervals = max(want if math.isinf(want) else math.ceil(want), float(m + 1))
+            bound = min(math.floor(float(n_in[k] - 1) * max_factor), float(sr.MAX_POINTS - 1))
+            if intervals > bound:
+                intervals, capped[k], status[k] = bound, True, capi.STRETCH_CAPPED
+            new = int(intervals) + 1
+            if new == n2[k]:
+                continue
+            n2[k], rounds[k], again = new, rounds[k] + 1, True
+        if not again:
+            break
+    report = np.zeros(K, dtype=capi.STRETCH_DTYPE)
+    final = np.zeros(K, dtype=capi.AUDIT_DTYPE)
+    recs = np.zeros(K, dtype=capi.TSCALE_DTYPE)
+    out = []
+    for k in range(K):
+        report[k] = (n_in[k], n2[k], 1.0 if n_in[k] < 2 else float(n2[k] - 1) / float(n_in[k] - 1), rounds[k], status[k])
+        w, recs[k], final[k] = evaluate(k, n2[k])
+        out.append(w)
+    return out, report, final, recs
+
+
+# ---- the synthetic ragged batch of the rounds (tests/test_tscale_cpu.py and tests/test_gpu_tscale.py share it) -----------------
+BP = capi.TSCALE_BLOCK_POINTS
+H = 0.008
+SYNTH_LENGTHS = [BP + 1, 0, 2, 3 * BP + 5, 1, 300, 90, 2 * BP, 333]
+SYNTH_AMPS = [0.05, 0, 1.0, 0.9, 0, 2.5, 0.3, 4.0, 0.2]
+SYNTH_W = [1.0, 1.3, 0.7, 2.0, 0.5, 0.9, 1.6, 1.1]
+
+
+def synth_steps(K):
+    return np.array([H * (1 + 0.1 * k) for k in range(K)])
+
+
+def synth_rows(model, lengths=SYNTH_LENGTHS, amps=SYNTH_AMPS):
+    """smooth joint rows with amplitudes of their own, one path with a kink in velocity, paths too short to differentiate, an empty one"""
+    nl = model.n_links
+    span = 60.0 if model.degrees else 1.0
+    rng = np.random.default_rng(41 + nl)
+    w = np.array(SYNTH_W[:nl])
+    rows = []
+    for k, n in enumerate(lengths):
+        t = np.arange(n) * H
+        r = span * amps[k] * np.sin(np.outer(w, t) * 2.0 + rng.uniform(0, 3, (nl, 1))) if n else np.zeros((nl, 0))
+        if k == 6:      # a kink: the joint stands, then moves at constant velocity
+            r[0] = np.where(np.arange(n) < 45, 0.0, (np.arange(n) - 45) * H * 0.8 * span)
+        rows.append(np.ascontiguousarray(r))
+    return rows
+
+
+def synth_problem(oracle_lib, model, rows, sres, d_path=3, scale=1.0):
+    """joint velocity and acceleration limits that some paths exceed, and a torque range gravity fits into everywhere but the fast
+    paths do not: from the pieces of the batch itself (D of path d_path; scale < 1 / 1.1 brings gravity outside the range)"""
+    nl = model.n_links
+    span = 60.0 if model.degrees else 1.0
+    P = [pieces(oracle_lib, model, r, sres[k]) for k, r in enumerate(rows)]
+    gmax = np.max([np.abs(G).max(axis=1) for A, B, G in P if G.shape[1]], axis=0)
+    A, B, G = P[d_path]
+    d = np.abs(A + B).max(axis=1)
+    tmax = scale * (1.1 * gmax + 0.5 * d + 1e-3)
+    tmin = -(0.8 * tmax + 0.3 * gmax)
+    return capi.make_problem(nl, 0, capi.ROBOT_GENJNT, capi.F_JNT_ACC_ON, jnt_vel_max=[3 * span] * nl, jnt_acc_max=[12 * span] * nl,
+                             jnt_trq_max=[float(v) for v in tmax], jnt_trq_min=[float(v) for v in tmin])
+
+
+def assert_records_equal(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    for k in range(got.shape[0]):
+        g, w = got[k], want[k]
+        assert g["s"].tobytes() == w["s"].tobytes() and all(int(g[c]) == int(w[c]) for c in ("at", "row", "side", "n_static", "reserved")), \
+            f"{what}: path {k}: got {tuple(g.tolist())}, want {tuple(w.tolist())}"
+    assert got.tobytes() == want.tobytes(), what
