@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "batotp_hip_audit.h"
+#include "output_plan.h" // PathBlock
 
 namespace bk
 {
@@ -44,11 +45,6 @@ struct AuditPath
    int64_t n;     // points
    int64_t pOff;  // first partial of the path
    double c1, c2; // 1 / (2 h), 1 / (h h)
-};
-
-struct AuditBlock
-{
-   int32_t path, blk; // points [blk * AUDIT_BP, (blk + 1) * AUDIT_BP) of the path; partial pOff + blk
 };
 
 struct AuditPartial
@@ -98,7 +94,7 @@ __device__ __forceinline__ long long audit_wave_sum(long long x)
    return x;
 }
 
-__global__ __launch_bounds__(AUDIT_THREADS) void k_audit_blocks(AuditConst C, const AuditPath *__restrict__ paths, const AuditBlock *__restrict__ blocks,
+__global__ __launch_bounds__(AUDIT_THREADS) void k_audit_blocks(AuditConst C, const AuditPath *__restrict__ paths, const PathBlock *__restrict__ blocks,
                                                                 int nBlocks, const double *__restrict__ rows, AuditPartial *__restrict__ partials)
 {
    __shared__ double tile[2][AUDIT_BP + 2];
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(AUDIT_THREADS) void k_audit_blocks(AuditConst C, co
    __shared__ long long redN[NW][2];
 
    if ((int)blockIdx.x >= nBlocks) return;
-   const AuditBlock bd = blocks[blockIdx.x];
+   const PathBlock bd = blocks[blockIdx.x]; // points [blk * AUDIT_BP, (blk + 1) * AUDIT_BP) of the path; partial pOff + blk
    const AuditPath pd = paths[bd.path];
    const int t = (int)threadIdx.x;
    const int64_t n = pd.n, p0 = (int64_t)bd.blk * AUDIT_BP;

@@ -60,7 +60,7 @@ static int auditConst(const batotp_output *o, const batotp_problem *prob, double
 // The two kernels of an audit -- k_audit_blocks on the table of block descriptors, k_audit_finish with a wavefront per path.  Every
 // audit goes through this function, the ones of outputs made by batotp_hip_output_from_rows (the known-answer route of the tests)
 // included: a test of that entry point is a test of the grids the product uses.
-static void launchAudit(hipStream_t st, const AuditConst &C, const AuditPath *dPaths, int K, const AuditBlock *dBlocks, int64_t nBlocks,
+static void launchAudit(hipStream_t st, const AuditConst &C, const AuditPath *dPaths, int K, const PathBlock *dBlocks, int64_t nBlocks,
                         const double *rows, AuditPartial *dPartials, batotp_path_audit *dOut)
 {
    if (nBlocks > 0)
@@ -81,40 +81,35 @@ static int auditRun(batotp_output *o, const batotp_problem *prob, double tol, vo
    hipStream_t st = ctx->stream;
 
    std::vector<AuditPath> paths((size_t)K);
-   int64_t nBlocks = 0;
+   std::vector<PathBlock> blocks;
+   std::vector<int64_t> first;
+   if (!pathBlocks(o->n.data(), 0, K, AUDIT_BP, blocks, first)) { snprintf(g_err, sizeof(g_err), "audit: too many blocks"); return BATOTP_ERR_ARG; }
+   const int64_t nBlocks = (int64_t)blocks.size();
    for (int k = 0; k < K; ++k)
    {
       const double h = o->sres[k];
       AuditPath &p = paths[k];
-      p.off = o->off[k]; p.n = o->n[k]; p.pOff = nBlocks;
+      p.off = o->off[k]; p.n = o->n[k]; p.pOff = first[k];
       p.c1 = 1.0 / (2.0 * h); p.c2 = 1.0 / (h * h);
-      nBlocks += (o->n[k] + AUDIT_BP - 1) / AUDIT_BP;
-   }
-   if (nBlocks > 0x7fffffff) { snprintf(g_err, sizeof(g_err), "audit: too many blocks"); return BATOTP_ERR_ARG; }
-   std::vector<AuditBlock> blocks((size_t)nBlocks);
-   for (int k = 0; k < K; ++k)
-   {
-      const int64_t nb = (o->n[k] + AUDIT_BP - 1) / AUDIT_BP;
-      for (int64_t b = 0; b < nb; ++b) blocks[(size_t)(paths[k].pOff + b)] = AuditBlock{k, (int32_t)b};
    }
 
-   const size_t need = granule(sizeof(AuditPath) * (size_t)K) + granule(sizeof(AuditBlock) * (size_t)nBlocks) +
+   const size_t need = granule(sizeof(AuditPath) * (size_t)K) + granule(sizeof(PathBlock) * (size_t)nBlocks) +
                        granule(sizeof(AuditPartial) * (size_t)nBlocks) + granule(sizeof(batotp_path_audit) * (size_t)K) + 4096;
    if ((rc = arenaReserve(ctx->ws[1], need, st))) return rc;
    if ((rc = poisonFill(ctx, ctx->ws[1].p, ctx->ws[1].cap, st))) return rc;
    Bump w;
    w.base = (char *)ctx->ws[1].p;
    AuditPath *dPaths = w.take<AuditPath>((size_t)K);
-   AuditBlock *dBlocks = w.take<AuditBlock>((size_t)nBlocks);
+   PathBlock *dBlocks = w.take<PathBlock>((size_t)nBlocks);
    AuditPartial *dPartials = w.take<AuditPartial>((size_t)nBlocks);
    batotp_path_audit *dOut = outDev ? (batotp_path_audit *)outDev : w.take<batotp_path_audit>((size_t)K);
    if (w.at > ctx->ws[1].cap) { snprintf(g_err, sizeof(g_err), "audit: scratch estimate exceeded"); return BATOTP_ERR_STATE; }
 
-   struct Event { hipEvent_t e = nullptr; ~Event() { if (e) hipEventDestroy(e); } } ev0, ev1;
+   Event ev0, ev1;
    HIP_TRY(hipEventCreate(&ev0.e));
    HIP_TRY(hipEventCreate(&ev1.e));
    HIP_TRY(hipMemcpyAsync(dPaths, paths.data(), sizeof(AuditPath) * (size_t)K, hipMemcpyHostToDevice, st));
-   if (nBlocks) HIP_TRY(hipMemcpyAsync(dBlocks, blocks.data(), sizeof(AuditBlock) * (size_t)nBlocks, hipMemcpyHostToDevice, st));
+   if (nBlocks) HIP_TRY(hipMemcpyAsync(dBlocks, blocks.data(), sizeof(PathBlock) * (size_t)nBlocks, hipMemcpyHostToDevice, st));
    HIP_TRY(hipEventRecord(ev0.e, st));
    launchAudit(st, C, dPaths, K, dBlocks, nBlocks, o->dTheta, dPartials, dOut);
    HIP_TRY(hipGetLastError());
@@ -168,8 +163,8 @@ extern "C" int batotp_hip_output_from_rows(batotp_ctx *ctx, int32_t n_paths, con
    *out = nullptr;
    int rc = bind(ctx);
    if (rc) return rc;
-   struct Owner { batotp_output *o; ~Owner() { batotp_hip_output_destroy(o); } } own{new (std::nothrow) batotp_output};
-   batotp_output *o = own.o;
+   OutputOwner own;
+   batotp_output *o = own.o = new (std::nothrow) batotp_output;
    if (!o) return BATOTP_ERR_ALLOC;
    o->ctx = ctx; o->K = n_paths; o->nJ = R; o->nTheta = n_theta; o->nCart = n_cart; o->nTrq = n_trq;
    o->n.assign(n_pts, n_pts + n_paths); o->sres.assign(sres, sres + n_paths); o->off.resize((size_t)n_paths);
@@ -189,7 +184,6 @@ extern "C" int batotp_hip_output_from_rows(batotp_ctx *ctx, int32_t n_paths, con
       HIP_TRY(hipMemcpyAsync(o->dTheta, rows, sizeof(double) * (size_t)(total * R), hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's rows are read until here
    }
-   *out = o;
-   own.o = nullptr;
+   *out = own.release();
    return BATOTP_OK;
 }

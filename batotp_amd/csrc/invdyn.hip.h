@@ -10,6 +10,8 @@
 // k_invdyn_pack   joint rows of an output with Cartesian rows, packed [n_links][n] per path for the host trig tables
 //                 (BATOTP_F_HOST_TRIG; an output without Cartesian rows already is that array).
 //
+// invdyn_point    everything a lane does for its point, shared with k_tscale (tscale.hip.h), which goes on from the three addends.
+//
 // Both passes are rnea_pass of kernels.hip.h exactly as the dynamics precompute calls it: the bits of a torque row are those of
 // a2 + a3 + a4 of k_dyn_serial for (q, dq/dt, d2q/dt2).
 #pragma once
@@ -17,6 +19,7 @@
 #include <stdint.h>
 #include "batotp_hip_invdyn.h"
 #include "kernels.hip.h"
+#include "output_plan.h" // PathBlock
 
 namespace bk
 {
@@ -24,6 +27,8 @@ namespace bk
 constexpr int INVDYN_BP = BATOTP_INVDYN_BLOCK_POINTS;
 constexpr int INVDYN_THREADS = INVDYN_BP; // one lane per point
 
+// the fields every torque kernel reads of a path; TscalePath (tscale.hip.h) begins with one, so a table of either is read through
+// invdyn_path_at with its own stride
 struct InvdynPath
 {
    int64_t off;   // first point of the path in the rows of the source and of the result (points)
@@ -32,41 +37,26 @@ struct InvdynPath
    double c1, c2; // 1 / (2 h), 1 / (h h)
 };
 
-struct InvdynBlock
+__device__ __forceinline__ const InvdynPath &invdyn_path_at(const void *paths, int stride, int k)
 {
-   int32_t path, blk; // points [blk * INVDYN_BP, (blk + 1) * INVDYN_BP) of the path (path: index into the range's descriptors)
-};
-
-__global__ __launch_bounds__(INVDYN_THREADS) void k_invdyn_pack(const InvdynPath *__restrict__ paths, const InvdynBlock *__restrict__ blocks, int nBlocks,
-                                                                const double *__restrict__ src, int nl, int nCart, double *__restrict__ pack)
-{
-   if ((int)blockIdx.x >= nBlocks) return;
-   const InvdynBlock bd = blocks[blockIdx.x];
-   const InvdynPath pd = paths[bd.path];
-   const int64_t n = pd.n, i = (int64_t)bd.blk * INVDYN_BP + (int)threadIdx.x;
-   if (i >= n) return;
-   const double *sb = src + pd.off * (nl + nCart);
-   double *pb = pack + pd.tOff * nl;
-   for (int j = 0; j < nl; ++j) pb[(int64_t)j * n + i] = sb[(int64_t)j * n + i];
+   return *reinterpret_cast<const InvdynPath *>(static_cast<const char *>(paths) + (int64_t)k * stride);
 }
 
-__global__ __launch_bounds__(INVDYN_THREADS) void k_invdyn(const batotp_serial_model *__restrict__ model, const InvdynPath *__restrict__ paths,
-                                                           const InvdynBlock *__restrict__ blocks, int nBlocks, const double *__restrict__ src, int nCart,
-                                                           const double *__restrict__ trig, double *__restrict__ dst)
+// cooperative copy of the chain model into LDS (8-byte words); the caller synchronises
+__device__ __forceinline__ void invdyn_stage_model(const batotp_serial_model *__restrict__ model, batotp_serial_model &sm)
 {
-   __shared__ batotp_serial_model sm;
-   {
-      // cooperative copy of the table (8-byte words)
-      const double *from = reinterpret_cast<const double *>(model);
-      double *to = reinterpret_cast<double *>(&sm);
-      for (int k = threadIdx.x; k < (int)(sizeof(batotp_serial_model) / 8); k += INVDYN_THREADS) to[k] = from[k];
-   }
-   __syncthreads();
-   if ((int)blockIdx.x >= nBlocks) return;
-   const InvdynBlock bd = blocks[blockIdx.x];
-   const InvdynPath pd = paths[bd.path];
-   const int64_t n = pd.n, i = (int64_t)bd.blk * INVDYN_BP + (int)threadIdx.x;
-   if (i >= n) return;
+   const double *from = reinterpret_cast<const double *>(model);
+   double *to = reinterpret_cast<double *>(&sm);
+   for (int k = threadIdx.x; k < (int)(sizeof(batotp_serial_model) / 8); k += INVDYN_THREADS) to[k] = from[k];
+}
+
+// Point i < pd.n of a path: copies its joint and Cartesian rows, writes its torque rows (t2 + fv qd) + t4 and leaves the three
+// addends of every joint of the model in t2, fvq and t4.  Every array is indexed by unrolled loops only: they stay in registers.
+__device__ __forceinline__ void invdyn_point(const batotp_serial_model &sm, const InvdynPath &pd, int64_t i, const double *__restrict__ src, int nCart,
+                                             const double *__restrict__ trig, double *__restrict__ dst, double (&t2)[BATOTP_MAX_LINKS],
+                                             double (&fvq)[BATOTP_MAX_LINKS], double (&t4)[BATOTP_MAX_LINKS])
+{
+   const int64_t n = pd.n;
    const int nl = sm.n_links, R = nl + nCart;
    const double *__restrict__ sb = src + pd.off * R;
    double *__restrict__ db = dst + pd.off * (R + nl);
@@ -106,12 +96,45 @@ __global__ __launch_bounds__(INVDYN_THREADS) void k_invdyn(const batotp_serial_m
 
    const double zero3[3] = {0, 0, 0};
    const double g0[3] = {-sm.gravity[0], -sm.gravity[1], -sm.gravity[2]};
-   double t2[BATOTP_MAX_LINKS], t4[BATOTP_MAX_LINKS];
    rnea_pass(sm, cq, sq, q1, q2, zero3, t2);
    rnea_pass(sm, cq, sq, z, z, g0, t4);
 #pragma unroll
    for (int j = 0; j < BATOTP_MAX_LINKS; ++j)
-      if (j < nl) db[(int64_t)(R + j) * n + i] = (t2[j] + sm.link[j].fv * q1[j]) + t4[j];
+      if (j < nl)
+      {
+         fvq[j] = sm.link[j].fv * q1[j];
+         db[(int64_t)(R + j) * n + i] = (t2[j] + fvq[j]) + t4[j];
+      }
+}
+
+// blocks: points [blk * INVDYN_BP, (blk + 1) * INVDYN_BP) of the path (path: index into the range's descriptors, pathStride bytes each)
+__global__ __launch_bounds__(INVDYN_THREADS) void k_invdyn_pack(const void *__restrict__ paths, int pathStride, const PathBlock *__restrict__ blocks, int nBlocks,
+                                                                const double *__restrict__ src, int nl, int nCart, double *__restrict__ pack)
+{
+   if ((int)blockIdx.x >= nBlocks) return;
+   const PathBlock bd = blocks[blockIdx.x];
+   const InvdynPath pd = invdyn_path_at(paths, pathStride, bd.path);
+   const int64_t n = pd.n, i = (int64_t)bd.blk * INVDYN_BP + (int)threadIdx.x;
+   if (i >= n) return;
+   const double *sb = src + pd.off * (nl + nCart);
+   double *pb = pack + pd.tOff * nl;
+   for (int j = 0; j < nl; ++j) pb[(int64_t)j * n + i] = sb[(int64_t)j * n + i];
+}
+
+__global__ __launch_bounds__(INVDYN_THREADS) void k_invdyn(const batotp_serial_model *__restrict__ model, const InvdynPath *__restrict__ paths,
+                                                           const PathBlock *__restrict__ blocks, int nBlocks, const double *__restrict__ src, int nCart,
+                                                           const double *__restrict__ trig, double *__restrict__ dst)
+{
+   __shared__ batotp_serial_model sm;
+   invdyn_stage_model(model, sm);
+   __syncthreads();
+   if ((int)blockIdx.x >= nBlocks) return;
+   const PathBlock bd = blocks[blockIdx.x];
+   const InvdynPath pd = paths[bd.path];
+   const int64_t i = (int64_t)bd.blk * INVDYN_BP + (int)threadIdx.x;
+   if (i >= pd.n) return;
+   double t2[BATOTP_MAX_LINKS], fvq[BATOTP_MAX_LINKS], t4[BATOTP_MAX_LINKS];
+   invdyn_point(sm, pd, i, src, nCart, trig, dst, t2, fvq, t4);
 }
 
 } // namespace bk

@@ -461,8 +461,8 @@ extern "C" int batotp_hip_output(batotp_batch *b, const batotp_output_params *pr
    OutPlan pl;
    planOutput(res.data() + path0, h.data(), K, path0, prm->out_res, prm->out_smooth_fact, pl);
 
-   struct Owner { batotp_output *o; ~Owner() { batotp_hip_output_destroy(o); } } own{new (std::nothrow) batotp_output};
-   batotp_output *o = own.o;
+   OutputOwner own;
+   batotp_output *o = own.o = new (std::nothrow) batotp_output;
    if (!o) return BATOTP_ERR_ALLOC;
    o->ctx = ctx; o->K = K; o->nJ = c.Rout; o->nTheta = c.nJ; o->nCart = c.pose ? 6 : c.nCartRows; o->nTrq = c.nTrqRows;
    o->n = pl.n; o->off = pl.off; o->sres = pl.sres;
@@ -483,7 +483,7 @@ extern "C" int batotp_hip_output(batotp_batch *b, const batotp_output_params *pr
    if (ctx->outBudget > 0) budget = (double)ctx->outBudget; // batotp_hip_set_workspace_budget
    cutChunks(pl, OutRows{c.R, c.cable || c.serialTrq, c.pose}, budget);
    if ((rc = arenaReserve(ctx->ws[1], pl.maxChunk + 4096, st))) return rc;
-   struct Event { hipEvent_t e = nullptr; ~Event() { if (e) hipEventDestroy(e); } } ev0, ev1;
+   Event ev0, ev1;
    HIP_TRY(hipEventCreate(&ev0.e));
    HIP_TRY(hipEventCreate(&ev1.e));
    HIP_TRY(hipEventRecord(ev0.e, st));

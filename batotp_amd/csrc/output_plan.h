@@ -3,6 +3,8 @@
 // sequence lie in its buffers.  All of it follows from the result rows of the forward sweep and the parameters of the call, so
 // nothing here touches the device: hipcc compiles this header into the library and a plain g++ -std=c++11 compiles it into
 // tests/drivers/output_plan_main.cpp, which compares the plan with the CPU checker (tests/test_output_plan.py).
+// cutRanges and pathBlocks -- the cut of a batch into ranges that fit a budget and the (path, block) grid of a range -- also serve the
+// outputs made from an output (range_run.inc), the audit and the resampler; tests/drivers/range_plan_main.cpp drives them alone.
 // The arithmetic is fp64 and (int) truncation of the reference's formulas (ba.cpp:1668-1683, 1841, 1876), in their order.
 #pragma once
 #include <algorithm>
@@ -125,23 +127,55 @@ inline size_t outScratchOf(const OutPath &q, const OutStep &S, const OutRows &m,
    return by;
 }
 
-// The chunks of the range: as many consecutive paths as fit `budget` bytes of scratch, at least one.  (Apart from planOutput
-// because the budget follows from the memory that is free once the result of the call is allocated, and the size of the result
-// is itself part of the plan.)
-inline void cutChunks(OutPlan &pl, const OutRows &m, double budget)
+// Ranges of consecutive items 0 .. K-1 whose scratch, need(k) bytes each, fits `budget` bytes, at least one item each: range c holds
+// the items [cuts[c], cuts[c + 1]).  Returns the bytes of the largest range.
+template <class Need> inline size_t cutRanges(int K, Need need, double budget, std::vector<int> &cuts)
 {
-   const int K = (int)pl.all.size();
-   pl.cuts.assign(1, 0);
-   pl.maxChunk = 0;
-   size_t bytes = 0;
+   cuts.assign(1, 0);
+   size_t bytes = 0, maxRange = 0;
    for (int k = 0; k < K; ++k)
    {
-      const size_t need = outScratchOf(pl.all[k], pl.step[k], m, pl.mixedCall);
-      if (k > pl.cuts.back() && (double)(bytes + need) > budget) { pl.cuts.push_back(k); bytes = 0; }
-      bytes += need;
-      pl.maxChunk = std::max(pl.maxChunk, bytes);
+      const size_t by = need(k);
+      if (k > cuts.back() && (double)(bytes + by) > budget) { cuts.push_back(k); bytes = 0; }
+      bytes += by;
+      maxRange = std::max(maxRange, bytes);
    }
-   pl.cuts.push_back(K);
+   cuts.push_back(K);
+   return maxRange;
+}
+
+// The chunks of the range.  (Apart from planOutput because the budget follows from the memory that is free once the result of
+// the call is allocated, and the size of the result is itself part of the plan.)
+inline void cutChunks(OutPlan &pl, const OutRows &m, double budget)
+{
+   pl.maxChunk = cutRanges((int)pl.all.size(), [&](int k) { return outScratchOf(pl.all[k], pl.step[k], m, pl.mixedCall); }, budget, pl.cuts);
+}
+
+// One workgroup of the audit, torque, stretch and scale kernels: block blk of path `path` of its range (read by those kernels).
+struct PathBlock
+{
+   int32_t path, blk;
+};
+
+inline int64_t blocksOf(int64_t n, int bp) { return (n + bp - 1) / bp; }
+
+// The grid of such a kernel over the paths [ka, kb) with n[k] points each, bp points a block: the blocks in path order and
+// first[k - ka], the place of the path's first block.  false where a path or the range has more than 2^31 - 1 blocks.
+inline bool pathBlocks(const int64_t *n, int ka, int kb, int bp, std::vector<PathBlock> &blocks, std::vector<int64_t> &first)
+{
+   blocks.clear();
+   first.assign((size_t)(kb - ka), 0);
+   int64_t total = 0;
+   for (int k = ka; k < kb; ++k)
+   {
+      first[k - ka] = total;
+      const int64_t nb = blocksOf(n[k], bp);
+      if (nb > 0x7fffffff || (total += nb) > 0x7fffffff) return false;
+   }
+   blocks.reserve((size_t)total);
+   for (int k = ka; k < kb; ++k)
+      for (int64_t b = 0, nb = blocksOf(n[k], bp); b < nb; ++b) blocks.push_back(PathBlock{k - ka, (int32_t)b});
+   return true;
 }
 
 // The paths of a chunk run route by route through one launch sequence each: at most four, whatever the number of paths and

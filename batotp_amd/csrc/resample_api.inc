@@ -81,6 +81,33 @@ struct Bump
 };
 size_t granule(size_t bytes) { return ((bytes ? bytes : 1) + 255) & ~(size_t)255; }
 
+// what a call holds until it returns, on every path out of it: an output it is making, an event, device memory of its own
+struct OutputOwner
+{
+   batotp_output *o = nullptr;
+   ~OutputOwner() { batotp_hip_output_destroy(o); }
+   batotp_output *release() { batotp_output *r = o; o = nullptr; return r; }
+};
+struct Event
+{
+   hipEvent_t e = nullptr;
+   ~Event() { if (e) hipEventDestroy(e); }
+};
+struct DevMem
+{
+   void *p = nullptr;
+   ~DevMem() { if (p) hipFree(p); }
+   int alloc(size_t bytes, const char *label) // label: "hipMalloc (...)" of the error text
+   {
+      hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
+      if (e == hipSuccess) return BATOTP_OK;
+      p = nullptr;
+      hipFail(e, label);
+      (void)hipGetLastError(); // reported; clear the sticky error
+      return BATOTP_ERR_ALLOC;
+   }
+};
+
 // diagnostic (batotp_hip_set_resample_trace, one-path calls): the order-independent checksum of `count` doubles at `ptr`, as
 // batotp_hip_resampled_checksums forms it, into slot `k` of the call's trace.  Where two evaluations of the same path disagree, the first
 // slot that differs names the stage -- and so the kernel -- that produced the difference.
@@ -615,19 +642,8 @@ static int resampleRun(batotp_ctx *ctx, const batotp_resample_params *prm, const
    double budget = 0.25 * (double)(freeB + ctx->ws[1].cap);
    if (budget > 48.0 * 1073741824.0) budget = 48.0 * 1073741824.0;
    if (ctx->rsBudget > 0) budget = (double)ctx->rsBudget; // batotp_hip_set_workspace_budget: the caller bounds the scratch memory
-   std::vector<int> cuts(1, 0);
-   size_t maxChunk = 0;
-   {
-      size_t bytes = 0;
-      for (int p = 0; p < B; ++p)
-      {
-         const size_t need = chunkBytesOfPath(p0[p], C);
-         if (p > cuts.back() && (double)(bytes + need) > budget) { cuts.push_back(p); bytes = 0; }
-         bytes += need;
-         if (bytes > maxChunk) maxChunk = bytes;
-      }
-      cuts.push_back(B);
-   }
+   std::vector<int> cuts;
+   const size_t maxChunk = cutRanges(B, [&](int p) { return chunkBytesOfPath(p0[p], C); }, budget, cuts);
    if ((rc = arenaReserve(ctx->ws[1], maxChunk, st))) return rc;
    // knots: first guess from the planned counts; rsChunk grows the workspace if a chunk does not fit
    {

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "batotp_hip_stretch.h"
+#include "output_plan.h" // PathBlock
 
 namespace bk
 {
@@ -32,17 +33,12 @@ struct StretchPath
    double rk;            // (double)(nIn - 1) / (double)(nOut - 1); unused where the path is copied
 };
 
-struct StretchBlock
-{
-   int32_t path, blk; // new points [blk * STRETCH_BP, (blk + 1) * STRETCH_BP) of the path (path: index into the range's descriptors)
-};
-
-__global__ __launch_bounds__(STRETCH_THREADS) void k_stretch(const StretchPath *__restrict__ paths, const StretchBlock *__restrict__ blocks, int nBlocks,
+__global__ __launch_bounds__(STRETCH_THREADS) void k_stretch(const StretchPath *__restrict__ paths, const PathBlock *__restrict__ blocks, int nBlocks,
                                                              const double *__restrict__ src, int R, double *__restrict__ dst)
 {
    __shared__ double tile[STRETCH_TILE_ROWS][STRETCH_TILE];
    if ((int)blockIdx.x >= nBlocks) return;
-   const StretchBlock bd = blocks[blockIdx.x];
+   const PathBlock bd = blocks[blockIdx.x]; // new points [blk * STRETCH_BP, (blk + 1) * STRETCH_BP) of path `path` of the range
    const StretchPath pd = paths[bd.path];
    const int64_t n = pd.nIn, n2 = pd.nOut, p0 = (int64_t)bd.blk * STRETCH_BP, p = p0 + (int)threadIdx.x;
    const double *__restrict__ sb = src + pd.offIn * R;

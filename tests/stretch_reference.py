@@ -65,8 +65,9 @@ def path_passes(rec, target):
     return ok, need
 
 
-def stretch_audit(rows_list, sres, n_theta, n_cart, prob, target=1.0, max_rounds=8, max_factor=16.0):
-    """the rounds of batotp_hip_output_stretch_audit: (stretched rows of every path, report as capi.STRETCH_DTYPE, final audit)"""
+def stretch_audit(rows_list, sres, n_theta, n_cart, prob, target=1.0, max_rounds=8, max_factor=16.0, trace=None):
+    """the rounds of batotp_hip_output_stretch_audit: (stretched rows of every path, report as capi.STRETCH_DTYPE, final audit).
+    trace: a list that takes, per round, (the audit records the round read, n_out, rounds, status) of every path after it"""
     K = len(rows_list)
     sres = np.broadcast_to(np.asarray(sres, dtype=np.float64), (K,))
     src = [np.ascontiguousarray(r, dtype=np.float64) for r in rows_list]
@@ -103,6 +104,8 @@ def stretch_audit(rows_list, sres, n_theta, n_cart, prob, target=1.0, max_rounds
             n2[k], rounds[k], again = new, rounds[k] + 1, True
             cur[k] = stretch_rows(src[k], new)      # always from the original rows
             stale[k] = True
+        if trace is not None:
+            trace.append((final.copy(), list(n2), list(rounds), list(status)))
         if not again:
             break
     report = np.zeros(K, dtype=capi.STRETCH_DTYPE)

@@ -107,6 +107,25 @@ def test_known_answers(hip_ctx, oracle_lib, name, n_cart, kind):
     out.close()
 
 
+@pytest.mark.parametrize("host_trig", [True, False], ids=["host_trig", "device_libm"])
+def test_rows_are_those_of_the_torque_rows(hip_ctx, oracle_lib, host_trig):
+    """k_tscale and k_invdyn run one body for a point: on the same output their rows are the same bytes, whichever trig they read"""
+    model, rows, sres, want, P = known_pieces(oracle_lib, "kuka", 3, "smooth")
+    nl = model.n_links
+    tmax, tmin = range_of(P, nl, 1.0)
+    prob = capi.make_problem(nl, 3, capi.ROBOT_GENJNT, 0, jnt_vel_max=[1.0] * nl, jnt_trq_max=tmax, jnt_trq_min=tmin)
+    out = capi.output_from_rows(hip_ctx, rows, sres, nl, 3, 0)
+    new, rec = out.torque_scale(prob, model, host_trig=host_trig)
+    trq = out.torques(model, host_trig=host_trig)
+    got, ref = new.all_rows(), trq.all_rows()
+    assert [r.shape for r in got] == [(2 * nl + 3, n) for n in LENGTHS] == [r.shape for r in ref]
+    for k, (g, w) in enumerate(zip(got, ref)):
+        assert g.tobytes() == w.tobytes(), f"path {k}"
+    assert sum(r.size for r in got) > 0 and all(np.isfinite(r).all() for r in got)
+    for o in (new, trq, out):
+        o.close()
+
+
 # ---- 2. steered roots ------------------------------------------------------------------------------------------------------
 def steered_paths():
     """one weightless link (G = 0, tau = J qdd + fv qd): short paths whose binding candidate is known by construction"""

@@ -109,10 +109,11 @@ def with_trq_on(prob):
     return p
 
 
-def stretch_torques(oracle_lib, model, rows_list, sres, n_cart, prob, target=1.0, max_rounds=8, max_factor=16.0, cache=None):
+def stretch_torques(oracle_lib, model, rows_list, sres, n_cart, prob, target=1.0, max_rounds=8, max_factor=16.0, cache=None, trace=None):
     """the rounds of batotp_hip_output_stretch_torques: (rows with torques of every path, report as capi.STRETCH_DTYPE, final audit,
     records as capi.TSCALE_DTYPE).  cache: a dict shared by calls on the SAME rows, model, limits and target -- what a path of a
-    given point count gives does not depend on the other arguments"""
+    given point count gives does not depend on the other arguments.  trace: a list that takes, per round, (the audit and the scale
+    records the round read, n_out, rounds, status) of every path after it"""
     K = len(rows_list)
     nl = model.n_links
     sres = np.broadcast_to(np.asarray(sres, dtype=np.float64), (K,))
@@ -131,8 +132,9 @@ def stretch_torques(oracle_lib, model, rows_list, sres, n_cart, prob, target=1.0
     n2, rounds, status, capped = list(n_in), [0] * K, [capi.STRETCH_PASSES] * K, [False] * K
     while True:
         again = False
+        read = [evaluate(k, n2[k])[1:] for k in range(K)]
         for k in range(K):
-            _, rec, aud = evaluate(k, n2[k])
+            rec, aud = read[k]
             kin_ok, need = sr.path_passes(aud, target)
             ok = kin_ok
             trq_ok = float(aud["fam"][capi.AUDIT_TRQ]["peak"]) <= target
@@ -162,6 +164,8 @@ def stretch_torques(oracle_lib, model, rows_list, sres, n_cart, prob, target=1.0
             if new == n2[k]:
                 continue
             n2[k], rounds[k], again = new, rounds[k] + 1, True
+        if trace is not None:
+            trace.append(([a for r, a in read], [r for r, a in read], list(n2), list(rounds), list(status)))
         if not again:
             break
     report = np.zeros(K, dtype=capi.STRETCH_DTYPE)

@@ -5,7 +5,7 @@
 
 The rows are the output of synth_gen7dof_s0 through the device pipeline (7402 points, 7 joint rows), tiled to --paths paths; the
 model is the built-in KUKA table; the torque range is +-(1.05 max|G| + 0.5 max|A + B| + 1e-3) of the rows' own torques (it binds, and gravity stays inside).
-torques_ms: k_invdyn (+ k_invdyn_pack with host tables).  tscale_ms: k_tscale + k_tscale_finish (+ k_tscale_pack)."""
+torques_ms: k_invdyn (+ k_invdyn_pack with host tables).  tscale_ms: k_tscale + k_tscale_finish (+ k_invdyn_pack)."""
 import argparse
 import os
 import statistics
