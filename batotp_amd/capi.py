@@ -914,6 +914,22 @@ def sdiv_kat(ctx: "Context", a: np.ndarray, b: np.ndarray):
     return q, w.astype(bool)
 
 
+def clamp_kat(ctx: "Context", raw, interp, cap, smin, lim1):
+    """(literal chain, one-instruction chain, validity flag) of the sweep prologue's clamp chain per operand tuple
+    (include/batotp_hip_clamp_kat.h; an entry point of the product library only)"""
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (raw, interp, cap, smin, lim1)]
+    n = arrs[0].size
+    assert all(a.size == n for a in arrs)
+    fn = ctx.library.lib.batotp_hip_clamp_kat
+    D = C.POINTER(C.c_double)
+    fn.argtypes = [C.c_void_p, C.c_int64, D, D, D, D, D, D, D, C.POINTER(C.c_int32)]
+    fn.restype = C.c_int
+    literal = np.empty(n); fast = np.empty(n); valid = np.empty(n, dtype=np.int32)
+    ctx.library.check(fn(ctx.handle, n, *[_dptr(a) for a in arrs], _dptr(literal), _dptr(fast),
+                         valid.ctypes.data_as(C.POINTER(C.c_int32))), "clamp_kat")
+    return literal, fast, valid.astype(bool)
+
+
 def out_segmax_kat(ctx: "Context", segs):
     """running maxima of the raw segment indices of several paths (findInterpSegs' cursor), through the output stage's launch function"""
     n1 = np.ascontiguousarray([len(x) for x in segs], dtype=np.int32)

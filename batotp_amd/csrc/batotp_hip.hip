@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "batotp_hip.h"
+#include "batotp_hip_clamp_kat.h"
 #include "batotp_models.h"
 #include "kernels.hip.h"
 #include "sweep1.hip.h"
@@ -635,6 +636,29 @@ extern "C" int batotp_hip_sdiv_kat(batotp_ctx *ctx, int64_t n, const double *a, 
    hipError_t e = hipStreamSynchronize(ctx->stream);
    hipFree(d);
    if (e != hipSuccess) return hipFail(e, "sdiv_kat");
+   return BATOTP_OK;
+}
+
+extern "C" int batotp_hip_clamp_kat(batotp_ctx *ctx, int64_t n, const double *raw, const double *interp, const double *cap, const double *smin,
+                                    const double *lim1, double *literal, double *fast, int32_t *valid)
+{
+   if (!ctx || n <= 0 || !raw || !interp || !cap || !smin || !lim1 || !literal || !fast || !valid) return BATOTP_ERR_ARG;
+   int rc = bind(ctx);
+   if (rc) return rc;
+   double *d = nullptr;
+   const size_t sz = sizeof(double) * (size_t)n;
+   HIP_TRY(hipMalloc((void **)&d, 8 * sz));
+   // every call and the launch are checked where they are made; the device block is released on every way out
+   struct Guard { double *p; ~Guard() { if (p) (void)hipFree(p); } } guard{d};
+   const double *in[5] = {raw, interp, cap, smin, lim1};
+   for (int k = 0; k < 5; ++k) HIP_TRY(hipMemcpyAsync(d + k * n, in[k], sz, hipMemcpyHostToDevice, ctx->stream));
+   hipLaunchKernelGGL(k_kat_clamp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n,
+                      d + 5 * n, d + 6 * n, reinterpret_cast<int *>(d + 7 * n));
+   HIP_TRY(hipGetLastError());
+   HIP_TRY(hipMemcpyAsync(literal, d + 5 * n, sz, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(hipMemcpyAsync(fast, d + 6 * n, sz, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(hipMemcpyAsync(valid, d + 7 * n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+   HIP_TRY(hipStreamSynchronize(ctx->stream));
    return BATOTP_OK;
 }
 

@@ -58,6 +58,52 @@ __device__ __forceinline__ double vmax_f64(double a, double b)
    return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The clamp chain of a stage's prologue (k_sweep8, k_sweep8_lock: "tableau combination" .. "sdotLim"; ba.cpp:1085, 1204-1236):
+//    vN = max(raw, floorV); [forward: m = max(interp, sdotMin); vN = vN > m ? m : vN;] vN = min(vN, sdotCap); vN = max(vN, sdotMin);
+//    vN = min(vN, lim1)
+// Written with dmin / dmax every clamp is v_cmp_f64 -> wait states for VCC -> two v_cndmask_b32, each waiting for the one before.
+// The one-instruction forms return the same bits when
+//    * no operand is a NaN: then compare-and-select and v_min / v_max return the same NUMBER, and the only representational
+//      difference is the zero they return for two zeros of opposite sign;
+//    * sdotMin > 0: a zero of either sign that the floor produces (raw = -0 against floorV = +0) only meets comparisons with
+//      positive numbers (max(interp, sdotMin) >= sdotMin) or with the cap, where its sign is immaterial for the verdict, and is
+//      replaced by max(., sdotMin) = sdotMin whatever its sign; lim1 is a fabs (or +inf) and vN >= sdotMin > 0 by then, so a zero
+//      result of the last clamp is lim1's own +0 either way.
+// floorV, sdotMin and sdotCap are per-path constants (clamp_consts_ok, once before the loop), lim1 is never a NaN (a NaN quotient
+// loses every compare of the literal form, and the fast quotient is finite inside the window of the shared reciprocal), so what is
+// left per stage is one v_cmp_u_f64 of the two raw values.  Where the condition fails the callers run the literal chain inside
+// the rare block they already have.  batotp_hip_clamp_kat / tests/test_gpu_stage_clamps.py check both chains and the flag on the
+// device against every combination of special operands.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool clamp_consts_ok(double floorV, double sdotMin, double sdotCap)
+{
+   return (floorV == floorV) & (sdotMin > 0.0) & (sdotCap == sdotCap);
+}
+// neither raw value is a NaN: one v_cmp_o_f64
+__device__ __forceinline__ bool clamp_raw_ok(double raw, double interp) { return !__builtin_isunordered(raw, interp); }
+// the chain up to and including max(., sdotMin); FWD: with the reverse curve's interpolated speed
+template <bool FWD>
+__device__ __forceinline__ double clamp_chain_literal(double raw, double interp, double floorV, double sdotMin, double sdotCap)
+{
+   double vN = dmax(raw, floorV);
+   if (FWD)
+   {
+      const double sdotMVC = dmax(interp, sdotMin);
+      vN = (vN > sdotMVC) ? sdotMVC : vN;
+   }
+   vN = dmin(vN, sdotCap);
+   return dmax(vN, sdotMin);
+}
+template <bool FWD>
+__device__ __forceinline__ double clamp_chain_fast(double raw, double interp, double floorV, double sdotMin, double sdotCap)
+{
+   double vN = vmax_f64(raw, floorV);
+   if (FWD) vN = vmin_f64(vN, vmax_f64(interp, sdotMin));
+   vN = vmin_f64(vN, sdotCap);
+   return vmax_f64(vN, sdotMin);
+}
+
 // All-reduce over the G lanes of a path group (G = 1, 2, 4, 8 or 16; groups are aligned to G lanes, so
 // every DPP source lane belongs to the same group and shares its control flow).
 template <int G>

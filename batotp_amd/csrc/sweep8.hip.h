@@ -45,6 +45,17 @@ constexpr int S8_BLOCK = 256;
 // "does any active lane ...": the i1 ballot intrinsic (HIP's __ballot goes through an integer compare: a v_cndmask + v_cmp per use)
 #define S8_ANY(x) (__builtin_amdgcn_ballot_w64(x) != 0)
 #define S8_RARE(x) __builtin_expect(S8_ANY(x), 0) // a guard whose block is off the straight-line code
+// The lane mask of ONE COMPARISON over the active lanes, as a 64-bit scalar.  The ballot of a comparison is the v_cmp itself; the ballot of
+// anything else (a & b, a bool that was assigned earlier, a bool that also feeds integer arithmetic) is lowered to v_cndmask_b32 v, 0, 1, mask
+// -> v_cmp_ne_u32 0, v: two vector instructions and their latency in front of a branch the whole wavefront waits for.  So a guard on several
+// conditions combines the masks of its comparisons with scalar & and | -- (S8_MASK(a) & S8_MASK(b)) != 0 -- and the per-lane bools serve the
+// selects only.  Every S8_MASK holds active lanes only; a mask carried from a place where more lanes were active (a per-lane constant, a
+// value of the previous stage) is always ANDed with one taken on the spot.
+typedef unsigned long long s8_mask;
+#define S8_MASK(cmp) __builtin_amdgcn_ballot_w64(cmp)
+#define S8_EXEC() __builtin_amdgcn_ballot_w64(true) // the active lanes
+// sdiv_window(x) (device_math.h) as a mask: the same two comparisons, so the compiler emits them once for the bool and the mask
+#define S8_MASK_WINDOW(x) (S8_MASK(fabs(x) >= SDIV_LO) & S8_MASK(fabs(x) <= SDIV_HI))
 // Measured and settled, no longer switches (DESIGN.md 4 has the numbers):
 //   kept: tableau combination without selects, stage values in LDS, walk pre-check, knot prefetch (round 4, profiles/r04_a_*)
 //   kept: the certified fast-forward in both directions (profiles/r04_j_*), in the reverse sweep as a phase of its own (profiles/r06_a_*)
@@ -57,6 +68,16 @@ constexpr int S8_BLOCK = 256;
 //         of a segment-change block and first read by the next such block (knot_window.h; both directions, G = 8 and 4, and k_sweep8_lock:
 //         headline reverse launch 3015 -> 2854 ms, forward launch 1538 -> 1410 ms, profiles/knot_window_*).  The knots are held as four
 //         scalars: the double2 selects of the literal route had cost the FEAT -1 kernels 80 bytes of scratch and two scratch stores per change.
+//   kept: the clamps of the prologue (floor, reverse curve's speed, sdotCap, sdotMin, lim1) as single v_max_f64 / v_min_f64 where no operand is
+//         a NaN and sdotMin > 0, the literal chain behind the rare guard the section already had (device_math.h, clamp_chain_fast; converted
+//         and unconverted clamps site by site: DESIGN.md 4, "The stage's clamps as single instructions"); in k_sweep8_lock also the exit test of the
+//         reverse-curve walk and that rare guard on the lane masks of their comparisons (S8_MASK above): headline forward launch 1408 -> 1337 ms
+//         (development builds: clamps 1407 -> 1359, guards -> 1342), the reverse launch does not move with the clamps; profiles/stage_chain_*
+//   kept: the replay loops of s8_certify with exit tests on the masks of their comparisons and no `more` carried between passes: headline reverse
+//         launch 2850 -> 2832 ms, 13 - 19 ms over two visits against a gate of 14 ms: at the edge of what a launch time tells, not claimed
+//   removed: the same treatment of the flat loop's own guards (threshold quotients, the check's rare guard, standing joint, chunk test): reverse
+//         launch 2852 -> 2892 ms, 41 ms SLOWER with four round trips fewer per pass (three to ten scalar instructions for each v_cndmask / v_cmp_ne
+//         pair); `odd` and the guards inside k_sweep8_lock's bisection block cost VGPRs in mask form (163 / 193 against 161 / 185) and stayed bools
 
 // (num / den) < thr as ratio_lt (kernels.hip.h) decides it, in two parts: the product form, and whether it was decisive
 __device__ __forceinline__ bool s8_ratio_lt_fast(double num, double den, double thr, bool &decided)
@@ -82,7 +103,6 @@ __device__ __forceinline__ void s8_ratio_lt_pair(double num1, double num2, doubl
    dec1 = ok & (lt1 | (num1 > den * (T1 * (1.0 + 1e-14))));
    dec2 = ok & (lt2 | (num2 > den * (T2 * (1.0 + 1e-14))));
 }
-
 // (the shared refined reciprocal of theta' -- sdiv_window / sdiv_rcp / sdiv_by -- lives in device_math.h.  In k_sweep1, the
 // one-path-per-wavefront kernel, the same technique measured 3-10 % SLOWER -- cfg 4: 961 against 874 ms -- and is not used there:
 // its window tests and ballot guards cost a lone wavefront more than the shorter quotients save; profiles/r04_b_*)
@@ -95,6 +115,20 @@ __global__ void k_kat_sdiv(int64_t n, const double *__restrict__ a, const double
    const bool ok = sdiv_window(a[i]) & sdiv_window(b[i]);
    inWindow[i] = ok ? 1 : 0;
    q[i] = ok ? sdiv_by(a[i], b[i], sdiv_rcp(b[i])) : a[i] / b[i];
+}
+
+// known-answer test of the prologue's clamp chain (device_math.h; batotp_hip_clamp_kat, include/batotp_hip_clamp_kat.h): the forward chain
+// with the floor +0 of every sweep, literally and through the one-instruction forms, and the condition under which the kernels take the latter
+__global__ void k_kat_clamp(int64_t n, const double *__restrict__ raw, const double *__restrict__ interp, const double *__restrict__ cap,
+                            const double *__restrict__ smin, const double *__restrict__ lim1, double *__restrict__ literal,
+                            double *__restrict__ fast, int *__restrict__ valid)
+{
+   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) return;
+   const double floorV = 0.0;
+   valid[i] = (clamp_consts_ok(floorV, smin[i], cap[i]) & clamp_raw_ok(raw[i], interp[i])) ? 1 : 0;
+   literal[i] = dmin(clamp_chain_literal<true>(raw[i], interp[i], floorV, smin[i], cap[i]), lim1[i]);
+   fast[i] = vmin_f64(clamp_chain_fast<true>(raw[i], interp[i], floorV, smin[i], cap[i]), lim1[i]);
 }
 
 // ---- CERTIFIED FAST-FORWARD of the bisection on the 8 lanes of a path (the certificate of k_sweep1, sweep1.hip.h: its derivation
@@ -192,15 +226,21 @@ __device__ __forceinline__ void s8_certify(bool jOn, double thD, double thD2, do
       // first round-6 build).  A lane that has stopped keeps its state through selects; its tests are re-evaluated on that unchanged
       // state and give what they gave.  Invariant used below: sdotTry == .5 * (sdotH + sdotL) in every lane at every point (the check
       // block's update, ba.cpp:1320, leaves it so, and every update here ends with that statement), so the midpoint needs no select.
+      // The exit tests of both loops combine the masks of their comparisons (S8_MASK above): mMore holds the lanes that go on and is what
+      // `more` is over the active lanes.  (S8_ANY(more) read the lane mask back from the 0/1 register that `it += more ? 1 : 0` had made of
+      // it: v_cndmask -> v_cmp_ne in front of the branch of a loop that is one dependent chain.)
+      // Neither `more` nor its mask is carried from pass to pass: a lane that has stopped keeps its state, so the comparisons that stopped
+      // it come out the same in every later pass (the invariant above) and `more & ...` is `...`.
       int it = nIter;
-      bool inBand = false, more = true;
+      bool inBand = false;
       // the search for a first feasible speed (ba.cpp:1281-1285): the bracket shrinks below every violated candidate
       for (;;)
       {
          const double c = sdotTry, d = c * c - xThr;   // c * c: sdotSQ of the check
          inBand = !((fabs(d) > bandThr) & (c > 1e-100));
-         more = more & !inBand & (d > 0.0) & (it < 90);
-         if (!S8_ANY(more)) break;
+         const bool more = (fabs(d) > bandThr) & (c > 1e-100) & (d > 0.0) & (it < 90);
+         const s8_mask mMore = S8_MASK(fabs(d) > bandThr) & S8_MASK(c > 1e-100) & S8_MASK(d > 0.0) & S8_MASK(it < 90);
+         if (mMore == 0) break;
          const double lf2 = lowFact * 2.0;
          const double lo = dmax(.999 * 0.0, (1.0 - lf2) * c);
          lowFact = more ? lf2 : lowFact;
@@ -212,6 +252,11 @@ __device__ __forceinline__ void s8_certify(bool jOn, double thD, double thD2, do
       // sdotTry is feasible for certain and the first such speed: ba.cpp:1294 compares it with sdotGood = 0 and goes on.  From
       // here the plain bisection (ba.cpp:1286-1303): sdotGood == sdotL throughout
       const bool bisect = !inBand & (it < 90);
+      // (its mask: inBand as the first loop left it is the comparisons of its last pass; a lane outside `bisect` stays out of the second loop.
+      //  The mask and the bool must never disagree: sdotTry * sdotTry - xThr here is the `d` of that last pass bit for bit -- the same two
+      //  operations on the same operands, and the translation unit is compiled with -ffp-contract=off, so neither can become an FMA -- and
+      //  the compiler emits the comparisons once for both, as it does inside the loops.)
+      const s8_mask mBisect = S8_MASK(fabs(sdotTry * sdotTry - xThr) > bandThr) & S8_MASK(sdotTry > 1e-100) & S8_MASK(it < 90);
       sdotGood = bisect ? sdotTry : sdotGood;
       nGood = bisect ? 1 : nGood;
       sdotL = bisect ? sdotTry : sdotL;
@@ -220,14 +265,15 @@ __device__ __forceinline__ void s8_certify(bool jOn, double thD, double thD2, do
       // ba.cpp:1294 is false for certain when |c - sdotGood| > 1e-3 c (1 + 3e-14); otherwise this candidate is, or may be, the
       // last one and gets the real check and the real test
       const double convThr = 1e-3 * (1.0 + 3e-14);
-      more = bisect;
       for (;;)
       {
          const double c = sdotTry, d = c * c - xThr;
          const bool viol = d > 0.0;
-         const bool goesOn = viol | (fabs(c - sdotL) > convThr * c);
-         more = more & (fabs(d) > bandThr) & goesOn & (it < 90);
-         if (!S8_ANY(more)) break;
+         const double gap = fabs(c - sdotL), thr = convThr * c;
+         const bool goesOn = viol | (gap > thr);
+         const bool more = bisect & (fabs(d) > bandThr) & goesOn & (it < 90);
+         const s8_mask mMore = mBisect & S8_MASK(fabs(d) > bandThr) & (S8_MASK(d > 0.0) | S8_MASK(gap > thr)) & S8_MASK(it < 90);
+         if (mMore == 0) break;
          sdotH = (more & viol) ? c : sdotH;
          sdotL = (more & !viol) ? c : sdotL;
          sdotTry = .5 * (sdotH + sdotL);
@@ -416,7 +462,14 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    double sN = 0, wN = 0;
    double lowFact = .01, sdotGood = 0, sdotL = 0, sdotH = 0, sdotTry = 0;
    int nGood = 0, nIter = 0;
-   bool wild = !(fabs(v0) < kInf) | !(fabs(w0) < kInf); // a non-finite stage value has been kept (sticky; see the tableau combination)
+   // A stage value that is not an ordinary number has been kept (sticky; see the tableau combination).  "Ordinary" ends at 1e290, well
+   // inside the finite range: then every partial sum of the tableau combination is finite (six terms with weights below 12), and
+   // v0 + h * sum is not a NaN for a finite h -- what the one-instruction clamps of the prologue need (device_math.h, clamp_chain_fast).
+   // The per-path part of their condition (sdotMin > 0, no NaN among the constants) rides in the same flag.
+   constexpr double S8_ORDINARY = 1e290;
+   // (The flag stays a per-lane bool and `odd` the ballot of a bool: kept as a sticky lane mask it costs the reverse kernel two VGPRs,
+   //  profiles/stage_chain_code_object.txt.)
+   bool wild = !(fabs(v0) < S8_ORDINARY) | !(fabs(w0) < S8_ORDINARY) | !(fabs(h) < kInf) | !clamp_consts_ok(floorV, sdotMin, sdotCap);
    bool stageFailed = false; // the bisection of the stage that ended failed: sddotArr[st] keeps its previous value (ba.cpp:1091 ignores the code)
    const int hold = a.hold;
 #ifdef S8_PROFILE
@@ -467,7 +520,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
             {
                phase = PH_FIRST;
                const double vN = sdotCur;
-               wild |= !(fabs(vN) < kInf) | !(fabs(wN) < kInf);
+               wild |= !(fabs(vN) < S8_ORDINARY) | !(fabs(wN) < S8_ORDINARY);
                // slot st keeps (vN, wN); a failed bisection leaves sddotArr[st] as it was (the w half goes to the spare slot 7);
                // stage 6 is kept in registers by the step end below (its writes go to the spare slot 7 as well)
                {
@@ -567,21 +620,28 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   { const double a5 = sdotT + bc[5] * v5, b5 = sddotT + bc[5] * w5; sdotT = (st > 5) ? a5 : sdotT; sddotT = (st > 5) ? b5 : sddotT; }
                }
                sN = s0v + h * sdotT;
-               double vN = v0 + h * sddotT;
-               vN = dmax(vN, floorV); // ba.cpp:1085
+               const double vRaw = v0 + h * sddotT;
                sCur = sN;
 
-               // ---- sdotLim, ba.cpp:1204-1236 (theta' of the PREVIOUS evaluation point) -----------------
+               // ---- the floor of ba.cpp:1085 and sdotLim, ba.cpp:1204-1236 (theta' of the PREVIOUS evaluation point) -----------------
+               // The clamps with sdotCap, sdotMin, the floor and lim1 take their one-instruction forms (device_math.h, clamp_chain_fast) unless
+               // `odd`: vRaw is not a NaN when every stage value is below 1e290 (`wild` is false), and the path's constants are part of
+               // `wild`.  The two clamps of the forward sweep that involve the reverse curve's speed stay compare-and-select: whether that
+               // speed is a NaN is only known after the walk below, behind `odd`'s ballot, and a guard of its own costs more than they do
+               // (k_sweep8_lock, whose guard comes after the walk, converts them too).
+               double vN = vmax_f64(vRaw, floorV);
+               double sdotRev = 0;
                if (DIR == 1)
                {
                   // evalsdot, ba.cpp:1590-1607
 #include "sweep8_mvcwalk.inc"
                   const double tauM = (sCur - mS0) / (mS1 - mS0);
-                  const double sdotMVC = dmax(mD0 + tauM * (mD1 - mD0), sdotMin);
+                  sdotRev = mD0 + tauM * (mD1 - mD0);
+                  const double sdotMVC = dmax(sdotRev, sdotMin);
                   vN = (vN > sdotMVC) ? sdotMVC : vN;
                }
-               vN = dmin(vN, sdotCap);
-               vN = dmax(vN, sdotMin);
+               vN = vmin_f64(vN, sdotCap);
+               vN = vmax_f64(vN, sdotMin);
                double lim1 = kInf;
                {
 #pragma unroll
@@ -594,6 +654,8 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                   }
                   if (odd)
                   {
+                     // the chain as the reference writes it, for every lane of the block
+                     vN = clamp_chain_literal<DIR == 1>(vRaw, sdotRev, floorV, sdotMin, sdotCap);
 #pragma unroll
                      for (int q = 0; q < PER; ++q)
                      {
@@ -601,9 +663,14 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                         const bool fast = rOk[q] & sdiv_window(vmax[q]);
                         if (on && !fast) lim1 = dmin(lim1, fabs(vmax[q] / thD[q]));
                      }
+                     lim1 = grp_min<G>(lim1);
+                     vN = dmin(vN, lim1);
                   }
-                  lim1 = grp_min<G>(lim1);
-                  vN = dmin(vN, lim1);
+                  else
+                  {
+                     lim1 = grp_min<G>(lim1);
+                     vN = vmin_f64(vN, lim1);
+                  }
                }
                sdotCur = vN;
                // applyAccelConstraintsBisectionPt, ba.cpp:1250-1265

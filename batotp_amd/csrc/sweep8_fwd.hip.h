@@ -121,6 +121,9 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    double thD = t.thD[0], thD2 = t.thD2[0];
    bool rOk = sdiv_window(thD);
    double rD = sdiv_rcp(thD);
+   // the lane masks the guards of a stage combine (S8_MASK, sweep8.hip.h): per-lane constants once, rOk beside the bool
+   s8_mask mROk = S8_MASK_WINDOW(thD);
+   const s8_mask mJOn = S8_MASK(j < t.nJ), mVmaxOk = S8_MASK_WINDOW(vmax);
    const bool accOn = (t.flags & BATOTP_F_JNT_ACC_ON) != 0;
    const double thrV = t.thrV, thrA = t.thrA, vfact = t.vfact, afact = t.afact;
    const double sdotCap = t.sdotCap, sddotMax = t.sddotMax, sdotMin = t.sdotMin;
@@ -161,6 +164,9 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    if (writer) { out[0] = make_double2(s0v, v0); mypts[0] = make_double2(s0v, v0); }
 
    const double floorV = 0.0 / absh; // ba.cpp:1050-1051,1085
+   // the clamp chain of the prologue may take its one-instruction form (device_math.h, clamp_chain_fast): the path's part of the condition
+   // (clamp_consts_ok's comparisons, as the mask the stage's guard combines)
+   const s8_mask mClampLit = ~(S8_MASK(floorV == floorV) & S8_MASK(sdotMin > 0.0) & S8_MASK(sdotCap == sdotCap));
    int i = 1;   // the step in progress; a path that reaches its end has i + 1 points
    unsigned endStatus = 0;
    bool alive = true;
@@ -296,33 +302,33 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
             if (st > 4) { sdotT += b4 * v4; sddotT += b4 * w4; }
             if (st > 5) { sdotT += b5 * v5; sddotT += b5 * w5; }
             sN = s0v + h * sdotT;
-            double vN = v0 + h * sddotT;
-            vN = dmax(vN, floorV); // ba.cpp:1085
+            const double vRaw = v0 + h * sddotT;
             sCur = sN;
 
-            // ---- sdotLim, ba.cpp:1204-1236 (theta' of the PREVIOUS evaluation point) -----------------
-            {
-               // evalsdot, ba.cpp:1590-1607
+            // ---- the floor of ba.cpp:1085 and sdotLim, ba.cpp:1204-1236 (theta' of the PREVIOUS evaluation point) -----------------
+            // evalsdot, ba.cpp:1590-1607
 #include "sweep8_mvcwalk.inc"
-               const double tauM = (sCur - mS0) / (mS1 - mS0);
-               const double sdotMVC = dmax(mD0 + tauM * (mD1 - mD0), sdotMin);
-               vN = (vN > sdotMVC) ? sdotMVC : vN;
-            }
-            vN = dmin(vN, sdotCap);
-            vN = dmax(vN, sdotMin);
+            const double tauM = (sCur - mS0) / (mS1 - mS0);
+            const double sdotRev = mD0 + tauM * (mD1 - mD0);
+            // max(., floorV), the reverse curve's speed (itself at least sdotMin), sdotCap, sdotMin: four v_max / v_min (device_math.h)
+            double vN = clamp_chain_fast<true>(vRaw, sdotRev, floorV, sdotMin, sdotCap);
             {
                double lim1 = kInf;
                const bool on = jOn && fabs(thD) > thrV;
                const bool fast = rOk & sdiv_window(vmax);
                const double qv = fabs(sdiv_by(vmax, thD, rD));
                lim1 = (on & fast) ? dmin(lim1, qv) : lim1;
-               // a velocity-limit quotient outside the window of the shared reciprocal
-               if (S8_RARE(on & !fast))
+               // the straight-line code first: the reduction and the last clamp for the ordinary case ...
+               vN = vmin_f64(vN, grp_min<G>(lim1));
+               // ... and ONE guard for what is rare here, which then forms vN again: a velocity-limit quotient outside the window of the shared
+               // reciprocal, and a clamp chain that must run literally (a NaN among its operands, sdotMin <= 0); the literal chain is right
+               // for every lane, so all lanes take it
+               const s8_mask mRareV = (mJOn & S8_MASK(fabs(thD) > thrV) & ~(mROk & mVmaxOk)) | (mClampLit & S8_EXEC()) | S8_MASK(!clamp_raw_ok(vRaw, sdotRev));
+               if (__builtin_expect(mRareV != 0, 0))
                {
                   if (on && !fast) lim1 = dmin(lim1, fabs(vmax / thD));
+                  vN = dmin(clamp_chain_literal<true>(vRaw, sdotRev, floorV, sdotMin, sdotCap), grp_min<G>(lim1));
                }
-               lim1 = grp_min<G>(lim1);
-               vN = dmin(vN, lim1);
             }
             sdotCur = vN;
             // applyAccelConstraintsBisectionPt, ba.cpp:1250-1265
@@ -406,6 +412,10 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
                thD = (c3x3 * tau2 + c2x2 * tau + c1) * vfact;
                thD2 = (c3x6 * tau + c2x2) * afact;
                rOk = sdiv_window(thD);
+               // (a wavefront-wide mask assigned inside `if (alive)` and carried across steps: only the bits of the lanes active HERE are
+               //  renewed, the bits of a lane that has died are stale from then on.  That is harmless because a dead lane never comes back
+               //  and every use ANDs the mask with a comparison taken on the spot, which holds active lanes only -- keep it so.)
+               mROk = S8_MASK_WINDOW(thD);
                rD = sdiv_rcp(thD);
             }
             S8_TICK(tB);

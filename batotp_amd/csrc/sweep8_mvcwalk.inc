@@ -10,7 +10,12 @@
    {
       const MvcMove mvM = mvc_window_test(sCur, segM, nMvc, mS0, mS1);
       status |= mvM.status;
-      if (!S8_ANY(mvM.up | mvM.dn)) break;
+      // "does any cursor move": mvM.up | mvM.dn over the wavefront, from the masks of the comparisons themselves (S8_MASK, sweep8.hip.h).
+      // up = !in & (sCur > s0) & (seg < n - 2) is (sCur > s0) & !(sCur <= s1) & (seg < n - 2): sCur > s0 implies sCur >= s0;
+      // dn = !in & (sCur < s0) & (seg > 0) is (sCur < s0) & (seg > 0): sCur < s0 implies !in
+      const s8_mask mUpM = S8_MASK(sCur > mS0) & S8_MASK(!(sCur <= mS1)) & S8_MASK(segM < nMvc - 2);
+      const s8_mask mDnM = S8_MASK(sCur < mS0) & S8_MASK(segM > 0);
+      if ((mUpM | mDnM) == 0) break;
       mvc_window_shift(mvM, segM, mSLo, mDLo, mS0, mD0, mS1, mD1, mSHi, mDHi);
       const double2 qLoM = mvc[mvc_window_lo(segM)], qHiM = mvc[mvc_window_hi(segM, nMvc)];
       mSLo = qLoM.x; mDLo = qLoM.y; mSHi = qHiM.x; mDHi = qHiM.y;
