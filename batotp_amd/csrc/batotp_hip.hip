@@ -18,6 +18,8 @@
 #include "batotp_hip_clamp_kat.h"
 #include "batotp_models.h"
 #include "kernels.hip.h"
+#include "sweep_frame.hip.h"
+#include "sweep_general.hip.h"
 #include "sweep1.hip.h"
 #include "sweep8.hip.h"
 #include "sweep8_fwd.hip.h"
@@ -120,8 +122,8 @@ struct batotp_ctx
    int overlap = 0;
    int sweepGroup = 0; // lanes per path in the sweep kernel; 0 = automatic
    int pathsPerWave = 0; // 0 = automatic
-   int sweepTouch[2] = {-1, -1}; // reverse, forward: -1 = automatic, else bit 0 rows, bit 1 reverse curve (kernels.hip.h touch_*)
-   int sweepHold[2] = {-2, -2}; // reverse, forward: -2 = automatic, -1 = nested stage / bisection loops, 0..8 = flat loop with this hold (kernels.hip.h)
+   int sweepTouch[2] = {-1, -1}; // reverse, forward: -1 = automatic, else bit 0 rows, bit 1 reverse curve (sweep_general.hip.h touch_*)
+   int sweepHold[2] = {-2, -2}; // reverse, forward: -2 = automatic, -1 = nested stage / bisection loops, 0..8 = flat loop with this hold (sweep_general.hip.h)
    // May the AUTOMATIC choice use the flat stage / bisection loop?  0 = not decided yet, 1 = yes (this library was built by the
    // toolchain the loop was validated with and the canary of flatLoopStatus agreed with the nested loops on this device),
    // -1 = built by another toolchain, -2 = the canary disagreed, -3 = the canary could not run
@@ -1293,15 +1295,9 @@ extern "C" int batotp_hip_pointwise_mvc(batotp_batch *b)
    const int64_t knotsPerBlock = grouped ? K3G_BLOCK / 8 : K3_BLOCK;
    const int64_t sliceKnots = (int64_t)1 << 27; // x 8 lanes = 2^30 threads per launch
    const unsigned grid = (unsigned)((b->totalKnots + knotsPerBlock - 1) / knotsPerBlock);
-   // (compact splines read their pair rows directly: no LDS tile, which would only cap the occupancy)
-   // LDS staging of the coefficient rows (coalesced copy, then conflict-free reads) is available but off: measured, it
-   // is the occupancy it costs that matters -- UR6 rows (C = 6) 90 ms with the tile, 60 ms reading the rows directly;
-   // cable robot (C = 18) 125 vs 53 ms.  BATOTP_K3_TILE=1 switches it on for experiments.
-   const bool useTile = false;
    // velocity / acceleration-only problems: the kernel written for them (same bits; batotp_hip_set_k3_form(ctx, 0) runs the general one)
    const int feat = featureLevel(b);
    const bool formVA = !grouped && b->ctx->k3Form == 1 && feat <= 0;
-   const size_t ldsBytes = useTile ? sizeof(double) * (size_t)bs * (size_t)(b->P.C * 4 + 2) : 0;
    // overlap: K3 reads what the precompute wrote and nothing reads K3's output before the caller downloads it, so it
    // can share the GPU with the sweeps (second stream, joined by get_results / synchronize / the next precompute)
    const bool async = b->ctx->overlap != 0 && !b->mvcInCurves; // in the curve slots the values must be complete before a sweep starts
@@ -1329,8 +1325,11 @@ extern "C" int batotp_hip_pointwise_mvc(batotp_batch *b)
                             k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef, b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots,
                             mvcSlot, b->ctx->fastForward);
       else
-         hipLaunchKernelGGL(k_pointwise<F>, dim3(grid), dim3(bs), ldsBytes, k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef,
-                            b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots, useTile ? 1 : 0, mvcSlot);
+         // every lane reads the coefficient row of its knot from HBM.  Staging a workgroup's rows in LDS first (coalesced copy, then
+         // conflict-free reads) measured slower for the occupancy it costs: UR6 rows (C = 6) 90 ms with the tile against 60 ms,
+         // cable robot (C = 18) 125 against 53 ms.
+         hipLaunchKernelGGL(k_pointwise<F>, dim3(grid), dim3(bs), 0, k3s, b->P, b->dPinfo, b->B, b->dP, b->dSC, b->dCoef,
+                            b->compact ? b->dKM : (double *)nullptr, mvcOut, b->totalKnots, mvcSlot);
    });
    hipEventRecord(b->ev[2][1], k3s);
    b->evValid[2] = true;

@@ -4,8 +4,9 @@
 //   k_spline_pairs / k_spline_sol / k_spline_series  the same Thomas solve leaving second derivatives (compact
 //                                                  splines of the hot path; resampler; output stage)
 //   k_pointwise, k_pointwise_grp                   per-knot max admissible sdot (K3)
-//   k_sweep<G, FEAT, UNI>                          reverse / forward sweep, G lanes per path (K4)
-// (resample.hip.h and output.hip.h hold the kernels of the stages before and after the hot path)
+//   Pt<G, FEAT, UNI>                               a point of a sweep: evaluation, constraint check, bisection (K4's arithmetic)
+// (the sweep kernels themselves: sweep_frame.hip.h -- what they share around their stage loops --, sweep_general.hip.h, sweep1.hip.h,
+//  sweep8.hip.h, sweep8_fwd.hip.h; resample.hip.h and output.hip.h hold the kernels of the stages before and after the hot path)
 //
 // Reference routines restated here (file:line under /root/reference/batotp):
 //   Spline::getSplineCoeffs spline.cpp:168-211, solveTriDiagNatural spline.cpp:252-276,
@@ -1695,35 +1696,13 @@ __global__ void __launch_bounds__(K3_BLOCK) k_pointwise(DevProblem P, const Path
                                                         const DevProblem *__restrict__ dP,
                                                         const double *__restrict__ sC, const double *__restrict__ coef,
                                                         const double *__restrict__ km,
-                                                        double *__restrict__ mvc, int64_t total, int useTile, int64_t mvcSlot)
+                                                        double *__restrict__ mvc, int64_t total, int64_t mvcSlot)
 {
    __shared__ double lim[6][8];
-   extern __shared__ double tile[]; // K3_BLOCK rows of C*4 doubles, padded by 2 doubles per row
    stage_limits(dP, lim);
 
-   // The coefficient rows of consecutive knots are contiguous in HBM (also across path boundaries):
-   // the workgroup copies its K3_BLOCK rows with fully coalesced 32-byte-per-lane loads into LDS,
-   // then every lane evaluates its own knot from LDS (row stride padded by 16 B: conflict-free b128 reads).
-   const int64_t g0 = (int64_t)blockIdx.x * K3_BLOCK;
-   const int rowD = P.C * 4, rowPad = rowD + 2;
-   const int rowsHere = (total - g0) < K3_BLOCK ? (int)(total - g0) : K3_BLOCK;
-   // (compact splines read their pair rows directly; so do wide rows -- torque problems -- whose tile would leave
-   // room for one wavefront per SIMD only: useTile is the host's choice)
-   if (FEAT >= 0 && useTile)
-   {
-      const Coef4 *__restrict__ srcp = reinterpret_cast<const Coef4 *>(coef + g0 * rowD);
-      const int chunks = rowsHere * P.C;
-      for (int k = threadIdx.x; k < chunks; k += K3_BLOCK)
-      {
-         const Coef4 v = srcp[k];
-         const int r = k / P.C, c = k - r * P.C;
-         double *dst = tile + r * rowPad + c * 4;
-         dst[0] = v.c0; dst[1] = v.c1; dst[2] = v.c2; dst[3] = v.c3;
-      }
-   }
-   __syncthreads();
-
-   const int64_t g = g0 + threadIdx.x;
+   const int rowD = P.C * 4;
+   const int64_t g = (int64_t)blockIdx.x * K3_BLOCK + threadIdx.x;
    if (g >= total) return;
    int lo = 0, hi = B - 1;
    while (lo < hi)
@@ -1748,17 +1727,12 @@ __global__ void __launch_bounds__(K3_BLOCK) k_pointwise(DevProblem P, const Path
    if (FEAT < 0) eval_partials_cached(t, 0);
    else
    {
-      const int rowLocal = (int)threadIdx.x - (i - t.segC); // the last knot of a path uses the previous row
       if (km != nullptr)
       {
          // all channels as pairs: the row of the knot's segment is formed channel by channel where it is read (emit_segment's formulas)
          eval_partials_src(t, 0, PairRowAt{reinterpret_cast<const double2 *>(km) + (pi.koff + t.segC) * P.C, P.C});
       }
-      else
-      {
-         const double *row = (useTile && rowLocal >= 0) ? (tile + rowLocal * rowPad) : (t.coef + (unsigned)(t.segC * rowD));
-         eval_partials_row(t, 0, row);
-      }
+      else eval_partials_row(t, 0, t.coef + (unsigned)(t.segC * rowD)); // (the last knot of a path uses the previous row)
    }
    double sdot = t.sdotCap;
    sdot_lim(t, 0, sdot);
@@ -1835,504 +1809,6 @@ __global__ void __launch_bounds__(K3G_BLOCK) k_pointwise_grp(DevProblem P, const
       o[2 * (int64_t)N + i] = t.sddotH;
    }
 }
-
-// ---------------------------------------------------------------------------------------------
-// K4: the sweep.  Wavefront = 64 lanes = up to 64/G paths (a.ppw of them are used: with few paths
-// in the batch it is faster to spread them over more wavefronts than to fill every lane).
-// ---------------------------------------------------------------------------------------------
-struct SweepArgs
-{
-   DevProblem P;
-   const DevProblem *dP;
-   const PathInfo *pinfo;
-   const double *sC;
-   const double *coef;
-   const double *km; // compact splines (FEAT == -1): [N][Cin][2] (value, second derivative) per path
-   double2 *rev;  // [B][cap]
-   double2 *fwd;  // [B][cap]
-   batotp_path_result *res;
-   int *sink;     // [B] consumer of the prefetch touches
-   double *prof;  // diagnostic build (BK_PROFILE_SECTIONS): 4 doubles per path
-   int64_t cap;
-   int B;
-   int dir;
-   int ppw;       // paths per wavefront, 1 .. 64/G
-   int hold;      // FLAT kernels: a stage is started once hold/8 of the wavefront's live paths wait for one
-   int touch;     // software prefetch: bit 0 = spline rows ahead of the cursor, bit 1 = reverse curve ahead of its cursor (forward sweep)
-   int ff;        // k_sweep1: certified fast-forward of the bisection (sweep1.hip.h), batotp_hip_set_fast_forward; k_sweep8: bit 0 forward, bit 1 reverse sweep
-   int holdc;     // k_sweep8, reverse sweep: the certificate block serves the paths waiting for it once holdc/8 of the wavefront's live paths do
-   // Ragged batches: launch slot k of the sweep processes path order[k] -- the paths sorted by knot count, longest
-   // first.  The hardware hands workgroups to the SIMDs in launch order as slots free up, so this is longest-processing-time-first
-   // scheduling for the kernels with a wavefront per path, and it puts paths of similar length into the same wavefront of the
-   // kernels that carry several (a wavefront lasts as long as its longest path).  nullptr: paths in the order given (all equally
-   // long, or batotp_hip_set_path_order(ctx, 0)).  Nothing in a path's own arithmetic or memory depends on its slot.
-   const int *order;
-};
-
-// Butcher tableau of ba.cpp:58-63 (_B[k][j]; stage j+1 uses column j)
-#define BK_B00 (1. / 5)
-#define BK_B01 (3. / 40)
-#define BK_B02 (44. / 45)
-#define BK_B03 (19372. / 6561)
-#define BK_B04 (9017. / 3168)
-#define BK_B05 (35. / 384)
-#define BK_B11 (9. / 40)
-#define BK_B12 (-56. / 15)
-#define BK_B13 (-25360. / 2187)
-#define BK_B14 (-355. / 33)
-#define BK_B15 (0.)
-#define BK_B22 (32. / 9)
-#define BK_B23 (64448. / 6561)
-#define BK_B24 (46732. / 5247)
-#define BK_B25 (500. / 1113)
-#define BK_B33 (-212. / 729)
-#define BK_B34 (49. / 176)
-#define BK_B35 (125. / 192)
-#define BK_B44 (-5103. / 18656)
-#define BK_B45 (-2187. / 6784)
-#define BK_B55 (11. / 84)
-
-// Software prefetch: the walk over the spline rows (and over the reverse curve) is monotone, so
-// every stage of the reverse sweep each lane of the group touches one 128-byte line of the next
-// kilobyte ahead of (below) the cursor.  The loaded word is consumed one stage later (t.sink), which keeps the load alive without
-// ever waiting on it, and by then the line sits in the vector L1 / L2 instead of HBM.
-template <int G, int FEAT, bool UNI>
-__device__ __forceinline__ int touch_ahead(const Pt<G, FEAT, UNI> &t, int j)
-{
-   const int linesAhead = 1 + (j & 7);
-   const int rowDoubles = t.C * 4;
-   int v = 0;
-   if (FEAT < 0)
-   {
-      // compact splines: rows of Cin pairs; same scheme as below on the pair stream
-      const int rowD = t.nIn * 2;
-      int off = t.segC * rowD + t.dir * linesAhead * 16;
-      const int hi = (t.n - 1) * rowD;
-      off = off < 0 ? 0 : (off > hi ? hi : off);
-      v = reinterpret_cast<const int *>(t.km)[2 * (unsigned)off];
-   }
-   else
-   {
-      // spline rows: byte offset of the current row, then +/- (1..8) lines
-      const int lastRow = t.n - 1;
-      int off = t.segC * rowDoubles + t.dir * linesAhead * 16; // in doubles (16 doubles = 128 B)
-      const int hi = lastRow * rowDoubles;
-      off = off < 0 ? 0 : (off > hi ? hi : off);
-      v = reinterpret_cast<const int *>(t.coef)[2 * (unsigned)off];
-   }
-   return v;
-}
-
-// the same for the reverse curve the forward sweep follows: (s, sdot) pairs, 8 points per 128-byte line, ascending walk
-template <int G, int FEAT, bool UNI>
-__device__ __forceinline__ int touch_curve_ahead(const Pt<G, FEAT, UNI> &t, int j)
-{
-   int off = t.segMVC * 2 + (1 + (j & 7)) * 16; // in doubles
-   const int hi = (t.nMvc - 1) * 2;
-   off = off > hi ? hi : off;
-   return reinterpret_cast<const int *>(t.mvc)[2 * (unsigned)off];
-}
-
-// A workgroup is 4 wavefronts (one per SIMD of a CU): with one-wavefront workgroups the dispatcher was
-// observed to stack several of them on the SIMDs of one CU while other CUs stayed empty.
-constexpr int K4_BLOCK = 256;
-constexpr int BK_SWEEP_WPE = 2; // waves per SIMD the register allocation of the narrow (FEAT <= 1) sweep kernels is tuned for
-// FLAT: the stage loop and the bisection loop are one loop in which every path of the wavefront is either
-// waiting for its next stage or inside a constraint check (see the comment at the loop).
-template <int G, int FEAT, bool UNI, bool FLAT = false>
-__global__ void __launch_bounds__(K4_BLOCK, (G > 1 && G < 8) ? 1 : (FEAT <= 1 && G > 1) ? BK_SWEEP_WPE : 2) k_sweep(SweepArgs a)
-{
-   __shared__ double lim[6][8];
-   __shared__ double rk[7][6]; // FLAT: rk[st][k] = weight of stage value k in stage st (column st-1 of ba.cpp:58-63), 0 for k >= st
-   if (FLAT && threadIdx.x < 42)
-   {
-      const double tab[42] = {0, 0, 0, 0, 0, 0,
-                              BK_B00, 0, 0, 0, 0, 0,
-                              BK_B01, BK_B11, 0, 0, 0, 0,
-                              BK_B02, BK_B12, BK_B22, 0, 0, 0,
-                              BK_B03, BK_B13, BK_B23, BK_B33, 0, 0,
-                              BK_B04, BK_B14, BK_B24, BK_B34, BK_B44, 0,
-                              BK_B05, BK_B15, BK_B25, BK_B35, BK_B45, BK_B55};
-      (&rk[0][0])[threadIdx.x] = tab[threadIdx.x];
-   }
-   stage_limits(a.dP, lim);
-
-   const int lane = threadIdx.x & 63;
-   const int wave = blockIdx.x * (K4_BLOCK / 64) + (threadIdx.x >> 6);
-   constexpr bool SPLIT = Pt<G, FEAT, UNI>::SPLIT;
-   constexpr bool SPEC = Pt<G, FEAT, UNI>::SPEC;
-   const int j = (SPLIT || SPEC) ? (lane & 7) : lane % G;   // joint owned by this lane
-   const int slot = lane / G;
-   const int pslot = wave * a.ppw + slot;
-   if (slot >= a.ppw || pslot >= a.B) return; // whole groups leave together; DPP never crosses groups
-   const int p = a.order ? a.order[pslot] : pslot;
-   const bool writer = (lane % G == 0);
-   const int dir = a.dir;
-   const PathInfo pi = a.pinfo[p];
-   const int n = (int)pi.n;
-   const int64_t cap = a.cap;
-
-   Pt<G, FEAT, UNI> t;
-   pt_init(t, a.P, pi, a.sC, a.coef, a.km, lim, j, dir);
-   t.side = SPLIT ? ((lane >> 3) & 1) : 0;
-   t.cslot = SPEC ? ((lane >> 3) & 3) : 0;
-   t.pbase = lane & ~(G - 1);
-
-   double2 *out = (dir == 1 ? a.fwd : a.rev) + (int64_t)p * cap; // may alias t.mvc (curves in place): no __restrict__
-   batotp_path_result *__restrict__ r = a.res + p;
-   if (dir == 1)
-   {
-      const int64_t nRev = r->n_rev;
-      if (nRev < 2)
-      {
-         // no reverse curve to follow (its sweep ended with an error status): nothing to integrate
-         if (writer) { r->n_fwd = 0; r->steps_fwd = 0; r->t_total = 0; r->status_fwd = r->status_rev | BATOTP_ST_CAPACITY; r->n_bisect_fail_fwd = 0; }
-         return;
-      }
-      t.mvc = reinterpret_cast<const double *>(a.rev + (int64_t)p * cap + (cap - nRev));
-      t.nMvc = (int)nRev;
-   }
-   // BATOTP_F_CURVES_IN_PLACE (forward sweep, a.fwd == a.rev): point i of the forward curve goes to slot i, reverse point m sits in
-   // slot cap - nRev + m.  The forward curve has at least as many points up to any s as the reverse curve, so slot i has been
-   // left behind by the reverse-curve cursor -- checked every step with 64 points of margin (the cursor's back-steps, the
-   // prefetch and the windows of k_sweep1 stay within 32; the register window of k_sweep8 / k_sweep8_lock, mvc_window.h, reads one
-   // point behind the cursor's segment and two ahead of it); a path that would run into live reverse points ends as if out of capacity.
-   const int64_t revStart = (dir == 1 && a.fwd == a.rev) ? cap - (int64_t)t.nMvc : ((int64_t)1 << 62);
-#define BK_CURVE_FULL(i) ((i) >= cap || (i) + 64 >= revStart + (int64_t)t.segMVC)
-
-   const double absh = pi.integ_res;
-   const double h = dir * absh;
-   const int64_t maxIntegSteps = (int64_t)floor(a.P.max_integ_time / pi.integ_res) + 1;
-   const double sEnd = UNI ? pi.sres_c * (double)(n - 1) : t.sC[n - 1];
-   double sLast;
-   double s0v, s6v = 0;                             // sArr[0], sArr[6] (the other stage positions are not reused)
-   double v0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0;   // sdotArr
-   double w0 = 0, w1 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0, w6 = 0; // sddotArr
-
-   if (dir == 1) { t.segC = 0; t.tauC = 0; s0v = 0; t.segMVC = 0; t.tauMVC = 0; sLast = sEnd; }
-   else { t.segC = n - 2; t.tauC = 1; s0v = sEnd; t.segMVC = n - 2; t.tauMVC = 1; sLast = 0; }
-   t.sCur = s0v;
-   t.sdotCur = 0;
-
-   // bootstrap, ba.cpp:1024-1041 (two passes of [bisection, velocity limit]; kept as a loop so
-   // that the point evaluation is instantiated once here and once in the stage loop)
-#pragma unroll 1
-   for (int pass = 0; pass < 2; ++pass)
-   {
-      accel_pt(t, j, w0);
-      if (pass == 0) { v0 = .1 * h * w0; t.sdotMin = v0; }
-      else v0 = t.sdotCur;
-      sdot_lim(t, j, v0);
-      if (pass == 0) { t.sdotMin = v0; t.sdotCur = v0; }
-   }
-
-   // point 0
-   double sPrev = s0v, sdPrev = v0; // last two published points, for the end snap
-   double sCurPt = s0v, sdCurPt = v0;
-   if (writer) out[dir == 1 ? 0 : cap - 1] = make_double2(s0v, v0);
-
-   // ba.cpp:1050-1051: dsMin uses sArr.back() == 0, hence every dsMinV[j]/absh is +0
-   const double floorV = 0.0 / absh;
-
-#ifdef BK_PROFILE_SECTIONS
-   const unsigned long long tstart = __builtin_readcyclecounter();
-#endif
-   int64_t nPts = 0, i = 1;
-   unsigned endStatus = 0;
-   int pf = 0, pf2 = 0;
-   if constexpr (FLAT)
-   {
-      // One loop instead of {stages {bisection iterations}}.  In the nested form a wavefront stays in the bisection
-      // loop of a stage as long as ANY of its paths does (24 % of the path-stages of a reverse sweep bisect, for
-      // 5-15 iterations; with 8 paths per wavefront nearly every stage has such a path) while the paths whose first
-      // check passed idle.  Here a path is either waiting for its next stage or inside a check, every pass of the
-      // loop runs one check for all paths that are inside one, and the stage prologue (tableau combination, velocity
-      // limit, spline evaluation) runs when a.hold/8 of the live paths are waiting for it, so that its cost is shared.
-      // Paths of a wavefront drift apart in stage and step; nothing in a path's own arithmetic or order changes.
-      int st = (dir == 1) ? 0 : 1;
-      // state of this lane's path: one integer in a vector register on purpose (separate booleans become lane masks in
-      // scalar registers that are merged under ever-changing exec masks across this loop)
-      constexpr int PH_FIRST = 0, PH_ENDED = 1, PH_CHECK = 2, PH_DEAD = 3; // waiting for its first stage / a stage has ended / inside a check / finished
-      int phase = PH_FIRST;
-      if (BK_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; phase = PH_DEAD; }
-      double sN = 0, wN = 0;
-      double lowFact = .01, sdotGood = 0, sdotL = 0, sdotH = 0, sdotTry = 0;
-      int nGood = 0; // feasible points seen by the current bisection (anyGoodIter of ba.cpp:1254 == nGood > 0)
-      int nIter = 0;
-      for (;;)
-      {
-         const unsigned long long mAlive = __ballot(phase != PH_DEAD);
-         if (mAlive == 0) break;
-         const unsigned long long mWait = __ballot(phase < PH_CHECK);
-         const bool startNow = (mWait == mAlive) || (__popcll(mWait) * 8 >= __popcll(mAlive) * a.hold);
-         if (startNow && phase < PH_CHECK)
-         {
-            if (phase == PH_ENDED)
-            {
-               // the stage that just ended: keep its values (done here, once for all paths that wait, rather than
-               // path by path at the pass in which each one's check ended)
-               phase = PH_FIRST;
-               const double vN = t.sdotCur;
-               v1 = (st == 1) ? vN : v1; w1 = (st == 1) ? wN : w1;
-               v2 = (st == 2) ? vN : v2; w2 = (st == 2) ? wN : w2;
-               v3 = (st == 3) ? vN : v3; w3 = (st == 3) ? wN : w3;
-               v4 = (st == 4) ? vN : v4; w4 = (st == 4) ? wN : w4;
-               v5 = (st == 5) ? vN : v5; w5 = (st == 5) ? wN : w5;
-               if (a.touch & 1)
-               {
-                  t.sink += pf;
-                  pf = touch_ahead(t, j);
-               }
-               if (st < 6) ++st;
-               else
-               {
-                  // FSAL shift and publish, ba.cpp:1096-1100 (stage 6: position sN, values vN, wN)
-                  s0v = sN; v0 = vN; w0 = wN; w6 = wN;
-                  sPrev = sCurPt; sdPrev = sdCurPt;
-                  sCurPt = s0v; sdCurPt = v0;
-                  if (writer) out[dir == 1 ? i : cap - 1 - i] = make_double2(s0v, v0);
-                  st = (dir == 1) ? 0 : 1;
-                  if (t.sCur * dir > sLast) { nPts = i + 1; phase = PH_DEAD; } // ba.cpp:1109-1115
-                  else if (i > maxIntegSteps) { endStatus = BATOTP_ST_MAX_INTEG_TIME; phase = PH_DEAD; } // ba.cpp:1117-1122
-                  else if (++i, BK_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; phase = PH_DEAD; }
-               }
-            }
-            if (phase != PH_DEAD)
-            {
-               if (st == 0)
-               {
-                  // forward predictor (ba.cpp:1055-1065): only the move of the reverse-curve cursor survives
-                  t.sCur = s0v + h * v0;
-                  mvc_walk(t);
-                  st = 1;
-               }
-               const double *bc = rk[st];
-               double sdotT = 0, sddotT = 0;
-               // stage st adds the terms k < st only (a stale stage value may be infinite: 0 * inf must not enter the sum)
-               sdotT += bc[0] * v0; sddotT += bc[0] * w0;
-               { const double a1 = sdotT + bc[1] * v1, b1 = sddotT + bc[1] * w1; sdotT = (st > 1) ? a1 : sdotT; sddotT = (st > 1) ? b1 : sddotT; }
-               { const double a2 = sdotT + bc[2] * v2, b2 = sddotT + bc[2] * w2; sdotT = (st > 2) ? a2 : sdotT; sddotT = (st > 2) ? b2 : sddotT; }
-               { const double a3 = sdotT + bc[3] * v3, b3 = sddotT + bc[3] * w3; sdotT = (st > 3) ? a3 : sdotT; sddotT = (st > 3) ? b3 : sddotT; }
-               { const double a4 = sdotT + bc[4] * v4, b4 = sddotT + bc[4] * w4; sdotT = (st > 4) ? a4 : sdotT; sddotT = (st > 4) ? b4 : sddotT; }
-               { const double a5 = sdotT + bc[5] * v5, b5 = sddotT + bc[5] * w5; sdotT = (st > 5) ? a5 : sdotT; sddotT = (st > 5) ? b5 : sddotT; }
-               sN = s0v + h * sdotT;
-               double vN = v0 + h * sddotT;
-               vN = dmax(vN, floorV); // ba.cpp:1085
-               t.sCur = sN;
-               sdot_lim(t, j, vN);
-               t.sdotCur = vN;
-               // sddotArr[st] keeps its previous value when the bisection fails (ba.cpp:1091 ignores the code)
-               wN = (st == 1) ? w1 : (st == 2) ? w2 : (st == 3) ? w3 : (st == 4) ? w4 : (st == 5) ? w5 : w6;
-               // applyAccelConstraintsBisectionPt, ba.cpp:1250-1265
-               lowFact = .01; sdotGood = 0; nGood = 0; sdotL = 0; sdotH = vN; sdotTry = vN; nIter = 0;
-               eval_partials(t, j);
-               phase = PH_CHECK;
-            }
-         }
-         if (phase == PH_CHECK)
-         {
-            // one pass of the loop of ba.cpp:1267-1321: the statements of apply_accel_bisection above, written as selects
-            // (no divergent branches around the few operations of the update)
-            const bool isViol = verify_second_order(t, j, sdotTry);
-            const bool first = (nIter == 0);
-            const bool good = !isViol && !first;                 // a feasible point after at least one violated one
-            const bool shrink = isViol && nGood == 0;            // ba.cpp:1281-1285: no feasible point known yet
-            const double lowFact2 = lowFact * 2.0;
-            const double sdotLShrunk = dmax(.999 * 0.0, (1.0 - lowFact2) * sdotTry);
-            // ba.cpp:1294-1303: two successive feasible points closer than 1e-3 (relative), or a negative one
-            const bool conv = good && (ratio_lt(fabs(sdotTry - sdotGood), sdotTry, .001) || sdotTry < 0.0);
-            const bool fin = (!isViol && first) || conv;
-            lowFact = shrink ? lowFact2 : lowFact;
-            sdotH = isViol ? sdotTry : sdotH;
-            sdotL = shrink ? sdotLShrunk : ((good && !conv) ? sdotTry : sdotL);
-            sdotGood = good ? sdotTry : sdotGood;
-            nGood += good ? 1 : 0;
-            t.sdotCur = conv ? sdotTry : t.sdotCur;
-            // ba.cpp:1305-1320
-            const bool collapsed = (nGood == 0) && ratio_lt(sdotH - sdotL, sdotH, 1e-20);
-            const bool failed = !fin && (nIter + 1 > 100 || sdotTry < 0.0 || collapsed);
-            nIter += fin ? 0 : 1;
-            sdotTry = (fin || failed) ? sdotTry : .5 * (sdotH + sdotL);
-            wN = fin ? ((dir == 1) ? t.sddotH : t.sddotL) : wN;
-            t.status |= failed ? (unsigned)BATOTP_ST_BISECT_FAIL : 0u;
-            t.nfail += failed ? 1 : 0;
-            phase = (fin || failed) ? PH_ENDED : phase;
-         }
-      }
-   }
-   else
-   {
-      // the nested form: stages, and inside every stage the bisection loop of accel_pt
-      bool done = false;
-      while (!done)
-      {
-         if (BK_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; break; }
-         const double sStart = t.sCur;
-         // st == 0: Euler predictor (ba.cpp:1055-1065).  Its sdot is overwritten by stage 6; all that
-         // survives is the move of the reverse-curve cursor inside evalsdot (forward sweep only).
-         // st == 1..6: the six stages of ba.cpp:1068-1094.  A real loop (not unrolled) keeps the
-         // kernel inside the instruction cache.
-#pragma unroll 1
-         for (int st = (dir == 1 ? 0 : 1); st < 7; ++st)
-         {
-            double sN, vN, sdotT = 0, sddotT = 0;
-            switch (st)
-            {
-            case 0: break;
-            case 1: sdotT += BK_B00 * v0; sddotT += BK_B00 * w0; break;
-            case 2: sdotT += BK_B01 * v0; sdotT += BK_B11 * v1; sddotT += BK_B01 * w0; sddotT += BK_B11 * w1; break;
-            case 3:
-               sdotT += BK_B02 * v0; sdotT += BK_B12 * v1; sdotT += BK_B22 * v2;
-               sddotT += BK_B02 * w0; sddotT += BK_B12 * w1; sddotT += BK_B22 * w2;
-               break;
-            case 4:
-               sdotT += BK_B03 * v0; sdotT += BK_B13 * v1; sdotT += BK_B23 * v2; sdotT += BK_B33 * v3;
-               sddotT += BK_B03 * w0; sddotT += BK_B13 * w1; sddotT += BK_B23 * w2; sddotT += BK_B33 * w3;
-               break;
-            case 5:
-               sdotT += BK_B04 * v0; sdotT += BK_B14 * v1; sdotT += BK_B24 * v2; sdotT += BK_B34 * v3; sdotT += BK_B44 * v4;
-               sddotT += BK_B04 * w0; sddotT += BK_B14 * w1; sddotT += BK_B24 * w2; sddotT += BK_B34 * w3; sddotT += BK_B44 * w4;
-               break;
-            default:
-               sdotT += BK_B05 * v0; sdotT += BK_B15 * v1; sdotT += BK_B25 * v2; sdotT += BK_B35 * v3; sdotT += BK_B45 * v4; sdotT += BK_B55 * v5;
-               sddotT += BK_B05 * w0; sddotT += BK_B15 * w1; sddotT += BK_B25 * w2; sddotT += BK_B35 * w3; sddotT += BK_B45 * w4; sddotT += BK_B55 * w5;
-               break;
-            }
-            if (st == 0)
-            {
-               // forward predictor: evalsdot's cursor walk at s0 + h*sdot0, nothing else is kept
-               t.sCur = s0v + h * v0;
-               mvc_walk(t);
-               t.sCur = sStart;
-               continue;
-            }
-            sN = s0v + h * sdotT;
-            vN = v0 + h * sddotT;
-            vN = dmax(vN, floorV); // ba.cpp:1085
-            t.sCur = sN;
-            BK_TICK(ta0);
-            sdot_lim(t, j, vN);
-            BK_TICK(ta1);
-            BK_ACC(t.cycA, ta0, ta1);
-            t.sdotCur = vN;
-            // sddotArr[st] keeps its previous value when the bisection fails (ba.cpp:1091 ignores the code)
-            double wN = (st == 1) ? w1 : (st == 2) ? w2 : (st == 3) ? w3 : (st == 4) ? w4 : (st == 5) ? w5 : w6;
-            BK_TICK(tc0);
-            accel_pt(t, j, wN);
-            BK_TICK(tc1);
-            BK_ACC(t.cycC, tc0, tc1);
-            vN = t.sdotCur;
-            switch (st)
-            {
-            case 1: v1 = vN; w1 = wN; break;
-            case 2: v2 = vN; w2 = wN; break;
-            case 3: v3 = vN; w3 = wN; break;
-            case 4: v4 = vN; w4 = wN; break;
-            case 5: v5 = vN; w5 = wN; break;
-            default: s6v = sN; v6 = vN; w6 = wN; break;
-            }
-            // reverse sweep only (descending addresses; measured: -17 % there, +5 % on the forward sweep,
-            // whose ascending walk finds the next lines already on their way): consume last stage's touch,
-            // issue the next one
-            if (a.touch & 1)
-            {
-               t.sink += pf;
-               pf = touch_ahead(t, j);
-            }
-            if (dir == 1 && (a.touch & 2))
-            {
-               t.sink += pf2;
-               pf2 = touch_curve_ahead(t, j);
-            }
-         }
-
-         // FSAL shift and publish, ba.cpp:1096-1100
-         s0v = s6v; v0 = v6; w0 = w6;
-         sPrev = sCurPt; sdPrev = sdCurPt;
-         sCurPt = s0v; sdCurPt = v0;
-         if (writer) out[dir == 1 ? i : cap - 1 - i] = make_double2(s0v, v0);
-
-         if (t.sCur * dir > sLast) { nPts = i + 1; done = true; } // ba.cpp:1109-1115
-         else if (i > maxIntegSteps) { endStatus = BATOTP_ST_MAX_INTEG_TIME; break; } // ba.cpp:1117-1122
-         else ++i;
-      }
-   }
-   if (writer) a.sink[p] = t.sink + pf + pf2;
-#ifdef BK_PROFILE_SECTIONS
-   if (writer) { const unsigned long long tend = __builtin_readcyclecounter(); a.prof[4 * p + 0] = (double)t.cycA; a.prof[4 * p + 1] = (double)t.cycB; a.prof[4 * p + 2] = (double)(t.cycC - t.cycB); a.prof[4 * p + 3] = (double)(tend - tstart); }
-#endif
-
-   unsigned status = t.status | endStatus;
-   if (endStatus != 0)
-   {
-      if (writer)
-      {
-         if (dir == 1) { r->n_fwd = 0; r->steps_fwd = i; r->t_total = 0; r->status_fwd = status; r->n_bisect_fail_fwd = t.nfail; }
-         else { r->n_rev = 0; r->steps_rev = i; r->t_rev = 0; r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = t.nfail; }
-      }
-      return;
-   }
-
-   // end snap onto sLast, ba.cpp:1132-1134; forward: last sdot <- reverse curve's last sdot, ba.cpp:1140
-   {
-      const double sRat = (sLast - sPrev) / (sCurPt - sPrev);
-      sdCurPt = sdPrev + sRat * (sdCurPt - sdPrev);
-      sCurPt = sLast;
-      if (dir == 1) sdCurPt = t.mvc[(t.nMvc - 1) * 2 + 1];
-      if (writer) out[dir == 1 ? nPts - 1 : cap - nPts] = make_double2(sCurPt, sdCurPt);
-   }
-   const double tElapsed = absh * (double)(nPts - 1); // ba.cpp:1112
-   int64_t nOut = nPts;
-
-   if (nPts < 4 && writer)
-   {
-      // ba.cpp:1171-1184: re-interpolate linearly in time to four points
-      double ps[3], pd[3], tIn[3];
-      for (int k = 0; k < (int)nPts; ++k)
-      {
-         // ascending-in-time order == integration order
-         const double2 q = (k == (int)nPts - 1) ? make_double2(sCurPt, sdCurPt) : out[dir == 1 ? k : cap - 1 - k];
-         ps[k] = q.x; pd[k] = q.y;
-         tIn[k] = absh * (double)k;
-      }
-      if (dir != 1)
-      {
-         // the reference reversed the arrays before this step (ba.cpp:1145-1146)
-         for (int k = 0; k < (int)nPts / 2; ++k)
-         {
-            swap_d(ps[k], ps[nPts - 1 - k]);
-            swap_d(pd[k], pd[nPts - 1 - k]);
-         }
-      }
-      const double tResNew = tIn[nPts - 1] / 3.;
-      double ns[4], nd[4];
-      int cur = 0;
-      for (int k = 0; k < 4; ++k)
-      {
-         const double tn = tResNew * (double)k;
-         while (!(tn < tIn[cur + 1] || cur == (int)nPts - 2)) ++cur;
-         const double tau = (tn - tIn[cur]) / (tIn[cur + 1] - tIn[cur]);
-         ns[k] = ps[cur] + (ps[cur + 1] - ps[cur]) * tau;
-         nd[k] = pd[cur] + (pd[cur + 1] - pd[cur]) * tau;
-      }
-      for (int k = 0; k < 4; ++k) out[dir == 1 ? k : cap - 4 + k] = make_double2(ns[k], nd[k]);
-   }
-   if (nPts < 4) { status |= BATOTP_ST_SHORT; nOut = 4; }
-
-   if (writer)
-   {
-      if (dir == 1)
-      {
-         r->n_fwd = nOut; r->steps_fwd = nPts - 1; r->t_total = tElapsed; r->status_fwd = status; r->n_bisect_fail_fwd = t.nfail;
-      }
-      else
-      {
-         r->n_rev = nOut; r->steps_rev = nPts - 1; r->t_rev = tElapsed;
-         r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = t.nfail;
-      }
-   }
-}
-#undef BK_CURVE_FULL
 
 // ---------------------------------------------------------------------------------------------
 // marshalling helpers: one channel between [4][N] (C-ABI) and the interleaved device layout

@@ -1,7 +1,7 @@
 // sweep1.hip.h -- the sweep of a path that has a wavefront to itself (the latency-bound regime: BASELINE configs 2, 3 and 4
 // as worded -- one trajectory, or up to ~2 k paths per GPU, which is also one GPU's share of config 5), on uniform knot sites,
 // for every constraint family except the torque limits of a parallel mechanism that was not converted (isPar2Ser = 0).
-// Same arithmetic, same order, same results as k_sweep (kernels.hip.h) -- BA::sweep and everything it calls, reference
+// Same arithmetic, same order, same results as k_sweep (sweep_general.hip.h) -- BA::sweep and everything it calls, reference
 // batotp/ba.cpp:979-1195, 1204-1236, 1248-1332, 1341-1439, 1449-1581, 1590-1652 -- written for the fewest instructions per
 // stage instead of for generality:
 //   * a lone wavefront issues a vector instruction every 4-8 cycles whatever its number of active lanes (MI355X_MICROARCH.md;
@@ -14,8 +14,9 @@
 //     either fast-forwarded (the certificate below) or evaluating four candidates of the reference's (deterministic) candidate sequence
 //     per pass, as the 32-lane layout of k_sweep does;
 //   * lanes: lane = slot * 8 + joint, 4 candidate slots x 8 joint lanes; the other 32 lanes of the wavefront exit.
+// The entry of a path and its ending are sweep_frame.hip.h's; the bootstrap runs on this kernel's own state and stays here.
 #pragma once
-#include "kernels.hip.h"
+#include "sweep_frame.hip.h"
 
 namespace bk
 {
@@ -138,7 +139,7 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
    const double sddotMax = 2 * sEnd / (absh * absh);   // ba.cpp:1257
    const double vmaxj = lim[0][j], amaxj = lim[1][j];
    const double tmaxj = lim[2][j], tminj = lim[3][j];
-   const int64_t maxIntegSteps = (int64_t)floor(a.P.max_integ_time / absh) + 1;
+   const int64_t maxIntegSteps = sweep_max_steps(a.P, pi);
 
    const double2 *__restrict__ km = (FEAT < 0) ? reinterpret_cast<const double2 *>(a.km) + pi.koff * nIn : nullptr;
    const double *__restrict__ coef = (FEAT < 0) ? nullptr : a.coef + pi.koff * C * 4;
@@ -155,7 +156,7 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
       const int64_t nRev = r->n_rev;
       if (nRev < 2)
       {
-         if (writer) { r->n_fwd = 0; r->steps_fwd = 0; r->t_total = 0; r->status_fwd = r->status_rev | BATOTP_ST_CAPACITY; r->n_bisect_fail_fwd = 0; }
+         sweep_no_reverse_curve(r, writer);
          return;
       }
       mvc = reinterpret_cast<const double *>(a.rev + (int64_t)p * cap + (cap - nRev));
@@ -1154,8 +1155,7 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
    }
 
    int64_t nPts = 0, i = 1;
-   // BATOTP_F_CURVES_IN_PLACE: see k_sweep (the forward curve overwrites reverse points its cursor has left behind)
-   const int64_t revStart = (DIR == 1 && a.fwd == a.rev) ? cap - (int64_t)nMvc : ((int64_t)1 << 62);
+   const int64_t revStart = sweep_rev_start(a, nMvc, DIR); // curves in place: the forward curve overwrites reverse points its cursor has left behind
    unsigned endStatus = 0;
    bool done = false;
 #ifdef BK_PROFILE_SECTIONS
@@ -1163,7 +1163,7 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
 #endif
    while (!done)
    {
-      if (S1_UNI(i >= cap || i + 64 >= revStart + (int64_t)segMVC)) { endStatus = BATOTP_ST_CAPACITY; break; }
+      if (S1_UNI(sweep_curve_full(i, cap, revStart, (int64_t)segMVC))) { endStatus = BATOTP_ST_CAPACITY; break; }
       if (DIR == 1) mvcWalk(s0v + h * v0); // Euler predictor, ba.cpp:1055-1065: only the move of the reverse-curve cursor survives
 
       S1_STAGE(BK_B00 * v0, BK_B00 * w0, v1, w1)
@@ -1201,70 +1201,25 @@ __global__ void __launch_bounds__(S1_BLOCK, ((FEAT == 2 && FF == 0 && PAIRS) || 
    status |= endStatus;
    if (endStatus != 0)
    {
-      if (writer)
-      {
-         if (DIR == 1) { r->n_fwd = 0; r->steps_fwd = i; r->t_total = 0; r->status_fwd = status; r->n_bisect_fail_fwd = nfail; }
-         else { r->n_rev = 0; r->steps_rev = i; r->t_rev = 0; r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = nfail; }
-      }
+      sweep_end_error(r, writer, DIR, i, status, nfail);
       return;
    }
 
-   // end snap onto sLast, ba.cpp:1132-1134; forward: last sdot <- reverse curve's last sdot, ba.cpp:1140
-   {
-      const double sRat = (sLast - sPrev) / (sCurPt - sPrev);
-      sdCurPt = sdPrev + sRat * (sdCurPt - sdPrev);
-      sCurPt = sLast;
-      if (DIR == 1) sdCurPt = mvc[(nMvc - 1) * 2 + 1];
-      if (writer) out[DIR == 1 ? nPts - 1 : cap - nPts] = make_double2(sCurPt, sdCurPt);
-   }
-   const double tElapsed = absh * (double)(nPts - 1); // ba.cpp:1112
+   sweep_end_snap(DIR, sLast, sPrev, sdPrev, sCurPt, sdCurPt, DIR == 1 ? mvc[(nMvc - 1) * 2 + 1] : 0.0);
+   if (writer) out[DIR == 1 ? nPts - 1 : cap - nPts] = make_double2(sCurPt, sdCurPt);
    int64_t nOut = nPts;
-
-   if (nPts < 4 && writer)
+   if (nPts < 4)
    {
-      // ba.cpp:1171-1184: re-interpolate linearly in time to four points
-      double ps[3], pd[3], tIn[3];
-      for (int k = 0; k < (int)nPts; ++k)
+      status |= BATOTP_ST_SHORT; nOut = 4;
+      if (writer)
       {
-         const double2 q = (k == (int)nPts - 1) ? make_double2(sCurPt, sdCurPt) : out[DIR == 1 ? k : cap - 1 - k];
-         ps[k] = q.x; pd[k] = q.y;
-         tIn[k] = absh * (double)k;
-      }
-      if (DIR != 1)
-      {
-         for (int k = 0; k < (int)nPts / 2; ++k)
-         {
-            swap_d(ps[k], ps[nPts - 1 - k]);
-            swap_d(pd[k], pd[nPts - 1 - k]);
-         }
-      }
-      const double tResNew = tIn[nPts - 1] / 3.;
-      double ns[4], nd[4];
-      int cur = 0;
-      for (int k = 0; k < 4; ++k)
-      {
-         const double tn = tResNew * (double)k;
-         while (!(tn < tIn[cur + 1] || cur == (int)nPts - 2)) ++cur;
-         const double tau = (tn - tIn[cur]) / (tIn[cur + 1] - tIn[cur]);
-         ns[k] = ps[cur] + (ps[cur + 1] - ps[cur]) * tau;
-         nd[k] = pd[cur] + (pd[cur + 1] - pd[cur]) * tau;
-      }
-      for (int k = 0; k < 4; ++k) out[DIR == 1 ? k : cap - 4 + k] = make_double2(ns[k], nd[k]);
-   }
-   if (nPts < 4) { status |= BATOTP_ST_SHORT; nOut = 4; }
-
-   if (writer)
-   {
-      if (DIR == 1)
-      {
-         r->n_fwd = nOut; r->steps_fwd = nPts - 1; r->t_total = tElapsed; r->status_fwd = status; r->n_bisect_fail_fwd = nfail;
-      }
-      else
-      {
-         r->n_rev = nOut; r->steps_rev = nPts - 1; r->t_rev = tElapsed;
-         r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = nfail;
+         // the points before the snapped one, from the curve
+         double2 pt[3];
+         for (int k = 0; k < 3; ++k) pt[k] = (k < (int)nPts - 1) ? out[DIR == 1 ? k : cap - 1 - k] : make_double2(sCurPt, sdCurPt);
+         sweep_short_to_four(DIR, (int)nPts, absh, pt, out, cap);
       }
    }
+   sweep_end_result(r, writer, DIR, nOut, nPts, absh, status, nfail);
 }
 
 } // namespace bk

@@ -1,5 +1,5 @@
 // sweep8.hip.h -- K4 for large batches of velocity / acceleration-only problems (round 4): the flat stage / bisection loop of
-// k_sweep<8, FEAT <= 0, true, true> (kernels.hip.h) written for the instruction count.
+// k_sweep<8, FEAT <= 0, true, true> (sweep_general.hip.h) written for the instruction count.
 //
 // Same decomposition: a path = 8 lanes (lane j = joint j), up to 8 paths per wavefront, every path of a wavefront is either
 // waiting for its next stage or inside a constraint check; a pass of the loop runs the stage prologue for the waiting paths
@@ -21,8 +21,9 @@
 //     stores (the reverse sweep's 16 384 descending streams lost their partly written lines from the L2 between the stores:
 //     3.0x the curve bytes written, profiles/r03_e).
 // Results are bit-identical to k_sweep's (every sweep test runs both; tests/test_gpu_parity.py, tests/test_gpu_fuzz.py).
+// The entry of a path, the tableau and the ending of a path are sweep_frame.hip.h's.
 #pragma once
-#include "kernels.hip.h"
+#include "sweep_frame.hip.h"
 #include "mvc_window.h"
 #include "knot_window.h"
 
@@ -292,20 +293,10 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    static_assert(G == 8 || G == 4, "lanes per path");
    constexpr int PER = 8 / G;
    __shared__ double lim[6][8];
-   __shared__ double rk[7][6];                 // rk[st][k] = weight of stage value k in stage st (column st-1 of ba.cpp:58-63), 0 for k >= st
+   __shared__ double rk[7][6];                 // the tableau by stage number (sweep_tableau_lds)
    __shared__ double2 pts[S8_BLOCK / G][4];    // curve points of a path waiting for their 64-byte store
    __shared__ double2 vw[S8_BLOCK / G][8];     // (v_k, w_k) of stage k = 1..5 of every path; slot 0 and 7: writes that must not land
-   if (threadIdx.x < 42)
-   {
-      const double tab[42] = {0, 0, 0, 0, 0, 0,
-                              BK_B00, 0, 0, 0, 0, 0,
-                              BK_B01, BK_B11, 0, 0, 0, 0,
-                              BK_B02, BK_B12, BK_B22, 0, 0, 0,
-                              BK_B03, BK_B13, BK_B23, BK_B33, 0, 0,
-                              BK_B04, BK_B14, BK_B24, BK_B34, BK_B44, 0,
-                              BK_B05, BK_B15, BK_B25, BK_B35, BK_B45, BK_B55};
-      (&rk[0][0])[threadIdx.x] = tab[threadIdx.x];
-   }
+   sweep_tableau_lds(rk);
    stage_limits(a.dP, lim);
 
    const int lane = threadIdx.x & 63;
@@ -336,7 +327,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
       const int64_t nRev = r->n_rev;
       if (nRev < 2)
       {
-         if (writer) { r->n_fwd = 0; r->steps_fwd = 0; r->t_total = 0; r->status_fwd = r->status_rev | BATOTP_ST_CAPACITY; r->n_bisect_fail_fwd = 0; }
+         sweep_no_reverse_curve(r, writer);
          return;
       }
       mvc = a.rev + (int64_t)p * cap + (cap - nRev);
@@ -344,30 +335,15 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
       t.mvc = reinterpret_cast<const double *>(mvc);
       t.nMvc = nMvc;
    }
-   // curves in place (kernels.hip.h, BK_CURVE_FULL): slot i must have been left behind by the reverse-curve cursor
-   const int64_t revStart = (DIR == 1 && a.fwd == a.rev) ? cap - (int64_t)nMvc : ((int64_t)1 << 62);
 
    const double absh = pi.integ_res;
    const double h = DIR * absh;
-   const int64_t maxIntegSteps = (int64_t)floor(a.P.max_integ_time / pi.integ_res) + 1;
    const double sres = pi.sres_c;
    const double sEnd = sres * (double)(n - 1);
    const double sLast = (DIR == 1) ? sEnd : 0.0;
    double s0v = (DIR == 1) ? 0.0 : sEnd;
    double v0, w0 = 0;
-   if (DIR == 1) { t.segC = 0; t.tauC = 0; t.segMVC = 0; t.tauMVC = 0; }
-   else { t.segC = n - 2; t.tauC = 1; t.segMVC = n - 2; t.tauMVC = 1; }
-   t.sCur = s0v;
-   t.sdotCur = 0;
-#pragma unroll 1
-   for (int pass = 0; pass < 2; ++pass)
-   {
-      accel_pt(t, j, w0);
-      if (pass == 0) { v0 = .1 * h * w0; t.sdotMin = v0; }
-      else v0 = t.sdotCur;
-      sdot_lim(t, j, v0);
-      if (pass == 0) { t.sdotMin = v0; t.sdotCur = v0; }
-   }
+   pt_bootstrap(t, j, DIR, n, h, s0v, v0, w0);
    const double vBoot = v0;
 
    // ---- the loop's own state -------------------------------------------------------------------
@@ -433,11 +409,12 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    double sPrev = s0v, sdPrev = v0, sCurPt = s0v, sdCurPt = v0; // last two published points, for the end snap
    double sCur = s0v; // traj.sCur
 
-   const int iMax = (maxIntegSteps > 0x3ffffff0) ? 0x3ffffff0 : (int)maxIntegSteps;
+   const int iMax = sweep_max_steps_int(a.P, pi);
    const int capI = (int)cap;
-   // first slot the forward curve must not reach: revStart + segM - 64 (in-place curves)
-   const int revStartI = (revStart > 0x3fffffff) ? 0x3fffffff : (int)revStart; // (the launcher keeps cap below 2^30)
-#define S8_CURVE_FULL(i) ((i) >= capI || (DIR == 1 && (i) + 64 >= revStartI + segM))
+   // curves in place: slot i must have been left behind by the reverse-curve cursor (the reverse sweep follows no curve and only
+   // tests the capacity in its loop)
+   const int revStartI = sweep_rev_start_int(a, nMvc, DIR);
+   const auto curveFull = [&](int at) { return DIR == 1 ? sweep_curve_full(at, capI, revStartI, segM) : at >= capI; };
 
    // point 0: straight to HBM, and into the group of four it belongs to
    {
@@ -458,7 +435,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    constexpr bool CERT = DIR == -1 && PER == 1;
    const int holdC = a.holdc;
    int phase = PH_ENDED;
-   if (S8_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; phase = PH_DEAD; }
+   if (curveFull(i)) { endStatus = BATOTP_ST_CAPACITY; phase = PH_DEAD; }
    double sN = 0, wN = 0;
    double lowFact = .01, sdotGood = 0, sdotL = 0, sdotH = 0, sdotTry = 0;
    int nGood = 0, nIter = 0;
@@ -548,7 +525,7 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
                      const bool late = !fin && (i > iMax);     // ba.cpp:1117-1122
                      nPts = fin ? i + 1 : nPts;
                      i = (fin || late) ? i : i + 1;
-                     const bool full = !fin && !late && S8_CURVE_FULL(i);
+                     const bool full = !fin && !late && curveFull(i);
                      endStatus = late ? (unsigned)BATOTP_ST_MAX_INTEG_TIME : (full ? (unsigned)BATOTP_ST_CAPACITY : endStatus);
                      phase = (fin || late || full) ? PH_DEAD : phase;
                      // a complete group of four points: one 64-byte store (not for the step that ends the path: its last
@@ -916,22 +893,11 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    status |= endStatus;
    if (endStatus != 0)
    {
-      if (writer)
-      {
-         if (DIR == 1) { r->n_fwd = 0; r->steps_fwd = i; r->t_total = 0; r->status_fwd = status; r->n_bisect_fail_fwd = nfail; }
-         else { r->n_rev = 0; r->steps_rev = i; r->t_rev = 0; r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = nfail; }
-      }
+      sweep_end_error(r, writer, DIR, i, status, nfail);
       return;
    }
 
-   // end snap onto sLast, ba.cpp:1132-1134; forward: last sdot <- reverse curve's last sdot, ba.cpp:1140
-   {
-      const double sRat = (sLast - sPrev) / (sCurPt - sPrev);
-      sdCurPt = sdPrev + sRat * (sdCurPt - sdPrev);
-      sCurPt = sLast;
-      if (DIR == 1) sdCurPt = mvc[nMvc - 1].y;
-   }
-   const double tElapsed = absh * (double)(nPts - 1); // ba.cpp:1112
+   sweep_end_snap(DIR, sLast, sPrev, sdPrev, sCurPt, sdCurPt, DIR == 1 ? mvc[nMvc - 1].y : 0.0);
    int64_t nOut = nPts;
 
    if (nPts >= 4)
@@ -947,52 +913,17 @@ __global__ void __launch_bounds__(S8_BLOCK, G == 8 ? 2 : 1) k_sweep8(SweepArgs a
    }
    else
    {
-      // ba.cpp:1171-1184: re-interpolate linearly in time to four points.  The points of so short a curve are all still
-      // here: point 0 = the start, point nPts-2 = (sPrev, sdPrev), point nPts-1 = the snapped end.
+      // The points of so short a curve are all still here: point 0 = the start, point nPts-2 = (sPrev, sdPrev), point nPts-1 = the
+      // snapped end.
       status |= BATOTP_ST_SHORT; nOut = 4;
       if (writer)
       {
-         double ps[3], pd[3], tIn[3];
-         const double sInit = (DIR == 1) ? 0.0 : sEnd;
-         for (int k = 0; k < nPts; ++k)
-         {
-            const double2 q = (k == nPts - 1) ? make_double2(sCurPt, sdCurPt) : (k == 0 ? make_double2(sInit, vBoot) : make_double2(sPrev, sdPrev));
-            ps[k] = q.x; pd[k] = q.y;
-            tIn[k] = absh * (double)k;
-         }
-         if (DIR != 1)
-         {
-            for (int k = 0; k < nPts / 2; ++k)
-            {
-               swap_d(ps[k], ps[nPts - 1 - k]);
-               swap_d(pd[k], pd[nPts - 1 - k]);
-            }
-         }
-         const double tResNew = tIn[nPts - 1] / 3.;
-         int cur = 0;
-         for (int k = 0; k < 4; ++k)
-         {
-            const double tn = tResNew * (double)k;
-            while (!(tn < tIn[cur + 1] || cur == nPts - 2)) ++cur;
-            const double tauR = (tn - tIn[cur]) / (tIn[cur + 1] - tIn[cur]);
-            out[DIR == 1 ? k : cap - 4 + k] = make_double2(ps[cur] + (ps[cur + 1] - ps[cur]) * tauR, pd[cur] + (pd[cur + 1] - pd[cur]) * tauR);
-         }
+         const double2 snapped = make_double2(sCurPt, sdCurPt);
+         const double2 pt[3] = {make_double2(DIR == 1 ? 0.0 : sEnd, vBoot), nPts == 2 ? snapped : make_double2(sPrev, sdPrev), snapped};
+         sweep_short_to_four(DIR, nPts, absh, pt, out, cap);
       }
    }
-
-   if (writer)
-   {
-      if (DIR == 1)
-      {
-         r->n_fwd = nOut; r->steps_fwd = nPts - 1; r->t_total = tElapsed; r->status_fwd = status; r->n_bisect_fail_fwd = nfail;
-      }
-      else
-      {
-         r->n_rev = nOut; r->steps_rev = nPts - 1; r->t_rev = tElapsed;
-         r->status_rev = (r->status_rev & BATOTP_ST_SEG_ERROR) | status; r->n_bisect_fail_rev = nfail;
-      }
-   }
+   sweep_end_result(r, writer, DIR, nOut, nPts, absh, status, nfail);
 }
-#undef S8_CURVE_FULL
 
 } // namespace bk

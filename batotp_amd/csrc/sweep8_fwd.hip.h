@@ -19,18 +19,18 @@
 // Kept as they are: the knot-cursor walk, the segment change over its window of two knots (knot_window.h, shared with k_sweep8: the
 // load of the knot beyond is issued by every live lane and first read by the wavefront's next segment change), sweep8_mvcwalk.inc (the walk
 // of the reverse-curve cursor over its register window, mvc_window.h: the one fragment both kernels include), the margin for curves in
-// place, the staging of four curve points in LDS, the certified fast-forward (s8_certify), the end snap, the short-curve tail and
-// the result row.
+// place, the staging of four curve points in LDS and the certified fast-forward (s8_certify); the entry of a path, the bootstrap and
+// the ending of a path are sweep_frame.hip.h's, as in every sweep kernel.
 // The arithmetic is a COPY of k_sweep8's with G = 8, DIR = +1 (shared are the walk's fragment and the two window headers, mvc_window.h and
 // knot_window.h; a shared fragment of anything else would have to leave k_sweep8's code as it is).  A change on either side belongs on both:
 //   here                                        sweep8.hip.h, k_sweep8
-//   setup, bootstrap, loop state                "stage_limits" .. "const int hold = a.hold" (lane mapping to the S8_PROFILE block)
+//   setup, loop state                           "stage_limits" .. "const int hold = a.hold" (lane mapping to the S8_PROFILE block)
 //   checkPass                                   the block `if (phase == PH_CHECK)`: check, one pass of the bisection, s8_certify
 //   tableau combination                         the `odd` (literal) branch of "tableau combination"
 //   sdotLim, cursor walk, segment change,       the same-named sections of the prologue block (`if (phase < PH_CHECK)`)
 //   theta' / theta''
 //   "the stage that ended", step end            "the stage that ended: keep its values", `if (stepEnd)`
-//   end status, end snap, short tail, result    everything after the loop
+//   flush of the last group of four             `if (nPts >= 4)` after the loop
 // Results are bit-identical to k_sweep8's and the oracle's (tests/test_gpu_sweep8_lockstep.py, and every test
 // that drives forward hold 8).
 #pragma once
@@ -79,35 +79,21 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    const int64_t nRev = r->n_rev;
    if (nRev < 2)
    {
-      if (writer) { r->n_fwd = 0; r->steps_fwd = 0; r->t_total = 0; r->status_fwd = r->status_rev | BATOTP_ST_CAPACITY; r->n_bisect_fail_fwd = 0; }
+      sweep_no_reverse_curve(r, writer);
       return;
    }
    const double2 *mvc = a.rev + (int64_t)p * cap + (cap - nRev); // the reverse curve the forward sweep follows
    const int nMvc = (int)nRev;
    t.mvc = reinterpret_cast<const double *>(mvc);
    t.nMvc = nMvc;
-   // curves in place (kernels.hip.h, BK_CURVE_FULL): slot i must have been left behind by the reverse-curve cursor
-   const int64_t revStart = (a.fwd == a.rev) ? cap - (int64_t)nMvc : ((int64_t)1 << 62);
 
    const double absh = pi.integ_res;
    const double h = absh;
-   const int64_t maxIntegSteps = (int64_t)floor(a.P.max_integ_time / pi.integ_res) + 1;
    const double sres = pi.sres_c;
    const double sEnd = sres * (double)(n - 1);
    double s0v = 0.0;
    double v0, w0 = 0;
-   t.segC = 0; t.tauC = 0; t.segMVC = 0; t.tauMVC = 0;
-   t.sCur = s0v;
-   t.sdotCur = 0;
-#pragma unroll 1
-   for (int pass = 0; pass < 2; ++pass)
-   {
-      accel_pt(t, j, w0);
-      if (pass == 0) { v0 = .1 * h * w0; t.sdotMin = v0; }
-      else v0 = t.sdotCur;
-      sdot_lim(t, j, v0);
-      if (pass == 0) { t.sdotMin = v0; t.sdotCur = v0; }
-   }
+   pt_bootstrap(t, j, DIR, n, h, s0v, v0, w0);
    const double vBoot = v0;
 
    // ---- the loop's own state (k_sweep8's, one joint per lane) -------------------------------------
@@ -154,11 +140,9 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    double w1 = 0, w2 = 0, w3 = 0, w4 = 0, w5 = 0, w6 = 0;
    double sCur = s0v; // traj.sCur
 
-   const int iMax = (maxIntegSteps > 0x3ffffff0) ? 0x3ffffff0 : (int)maxIntegSteps;
+   const int iMax = sweep_max_steps_int(a.P, pi);
    const int capI = (int)cap;
-   // first slot the forward curve must not reach: revStart + segM - 64 (in-place curves)
-   const int revStartI = (revStart > 0x3fffffff) ? 0x3fffffff : (int)revStart; // (the launcher keeps cap below 2^30)
-#define S8L_CURVE_FULL(i) ((i) >= capI || (i) + 64 >= revStartI + segM)
+   const int revStartI = sweep_rev_start_int(a, nMvc, DIR); // curves in place: slot i must have been left behind by the reverse-curve cursor
 
    // point 0: straight to HBM, and into the group of four it belongs to
    if (writer) { out[0] = make_double2(s0v, v0); mypts[0] = make_double2(s0v, v0); }
@@ -170,7 +154,7 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    int i = 1;   // the step in progress; a path that reaches its end has i + 1 points
    unsigned endStatus = 0;
    bool alive = true;
-   if (S8L_CURVE_FULL(i)) { endStatus = BATOTP_ST_CAPACITY; alive = false; }
+   if (sweep_curve_full(i, capI, revStartI, segM)) { endStatus = BATOTP_ST_CAPACITY; alive = false; }
    double sN = 0, wN = 0;
    double lowFact = .01, sdotGood = 0, sdotL = 0, sdotH = 0, sdotTry = 0;
    int nGood = 0, nIter = 0;
@@ -456,7 +440,7 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
             const bool fin = sCur > sres * (double)(lastSeg + 1); // ba.cpp:1109-1115 (the path end sres (n - 1), as below)
             const bool late = !fin && (i > iMax);     // ba.cpp:1117-1122
             i = (fin || late) ? i : i + 1;
-            const bool full = !fin && !late && S8L_CURVE_FULL(i);
+            const bool full = !fin && !late && sweep_curve_full(i, capI, revStartI, segM);
             endStatus = late ? (unsigned)BATOTP_ST_MAX_INTEG_TIME : (full ? (unsigned)BATOTP_ST_CAPACITY : endStatus);
             alive = !(fin || late || full);
             // a complete group of four points: one 64-byte store (not for the step that ends the path: its last point is
@@ -480,24 +464,17 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    status |= endStatus;
    if (endStatus != 0)
    {
-      if (writer) { r->n_fwd = 0; r->steps_fwd = i; r->t_total = 0; r->status_fwd = status; r->n_bisect_fail_fwd = nfail; }
+      sweep_end_error(r, writer, DIR, i, status, nfail);
       return;
    }
 
-   // end snap onto sLast, ba.cpp:1132-1134; last sdot <- reverse curve's last sdot, ba.cpp:1140.  The last two published points:
-   // (s0v, v0), and the one before it, which is still in the group of four in LDS (point 0 went there too)
+   // The last two published points: (s0v, v0), and the one before it, which is still in the group of four in LDS (point 0 went
+   // there too)
    const int nPts = i + 1;
    double sCurPt = s0v, sdCurPt = v0;
    const double2 qPrev = mypts[(nPts - 2) & 3];
    const double sPrev = qPrev.x, sdPrev = qPrev.y;
-   const double sLast = sEnd;
-   {
-      const double sRat = (sLast - sPrev) / (sCurPt - sPrev);
-      sdCurPt = sdPrev + sRat * (sdCurPt - sdPrev);
-      sCurPt = sLast;
-      sdCurPt = mvc[nMvc - 1].y;
-   }
-   const double tElapsed = absh * (double)(nPts - 1); // ba.cpp:1112
+   sweep_end_snap(DIR, sEnd, sPrev, sdPrev, sCurPt, sdCurPt, mvc[nMvc - 1].y);
    int64_t nOut = nPts;
 
    if (nPts >= 4)
@@ -511,32 +488,17 @@ __global__ void __launch_bounds__(S8_BLOCK, 2) k_sweep8_lock(SweepArgs a)
    }
    else
    {
-      // ba.cpp:1171-1184: re-interpolate linearly in time to four points.  The points of so short a curve are all still
-      // here: point 0 = the start, point nPts-2 = (sPrev, sdPrev), point nPts-1 = the snapped end.
+      // The points of so short a curve are all still here: point 0 = the start, point nPts-2 = (sPrev, sdPrev), point nPts-1 = the
+      // snapped end.
       status |= BATOTP_ST_SHORT; nOut = 4;
       if (writer)
       {
-         double ps[3], pd[3], tIn[3];
-         for (int k = 0; k < nPts; ++k)
-         {
-            const double2 q = (k == nPts - 1) ? make_double2(sCurPt, sdCurPt) : (k == 0 ? make_double2(0.0, vBoot) : make_double2(sPrev, sdPrev));
-            ps[k] = q.x; pd[k] = q.y;
-            tIn[k] = absh * (double)k;
-         }
-         const double tResNew = tIn[nPts - 1] / 3.;
-         int cur = 0;
-         for (int k = 0; k < 4; ++k)
-         {
-            const double tn = tResNew * (double)k;
-            while (!(tn < tIn[cur + 1] || cur == nPts - 2)) ++cur;
-            const double tauR = (tn - tIn[cur]) / (tIn[cur + 1] - tIn[cur]);
-            out[k] = make_double2(ps[cur] + (ps[cur + 1] - ps[cur]) * tauR, pd[cur] + (pd[cur + 1] - pd[cur]) * tauR);
-         }
+         const double2 snapped = make_double2(sCurPt, sdCurPt);
+         const double2 pt[3] = {make_double2(0.0, vBoot), nPts == 2 ? snapped : make_double2(sPrev, sdPrev), snapped};
+         sweep_short_to_four(DIR, nPts, absh, pt, out, cap);
       }
    }
-
-   if (writer) { r->n_fwd = nOut; r->steps_fwd = nPts - 1; r->t_total = tElapsed; r->status_fwd = status; r->n_bisect_fail_fwd = nfail; }
+   sweep_end_result(r, writer, DIR, nOut, nPts, absh, status, nfail);
 }
-#undef S8L_CURVE_FULL
 
 } // namespace bk

@@ -20,7 +20,8 @@ COMPACT = capi.F_NO_SAMPLES | capi.F_COMPACT_SPLINES
 
 def _run(ctx, prob, ys, sres, cap, integ=None, pointwise=False, hip=False):
     """knots -> precompute -> (pointwise values) -> both sweeps of one batch.  The reverse curve is fetched between the sweeps
-    (curves in place: the forward sweep consumes it).  Returns (result rows, reverse curves, forward curves, forward launch)."""
+    (curves in place: the forward sweep consumes it).  Returns (result rows, reverse curves, forward curves, forward launch);
+    hip="both": the last entry is (reverse launch, forward launch)."""
     b = capi.Batch(ctx, prob, [y.shape[1] for y in ys], cap)
     b.upload_knots(0, ys, sres)
     if integ is not None:
@@ -34,6 +35,8 @@ def _run(ctx, prob, ys, sres, cap, integ=None, pointwise=False, hip=False):
     res = b.results()
     fwd = [b.curve(k, +1) for k in range(len(ys))]
     launch = b.last_sweep_launch(+1) if hip else None
+    if hip == "both":
+        launch = (b.last_sweep_launch(-1), launch)
     b.close()
     return res, rev, fwd, launch
 
