@@ -241,6 +241,29 @@ TSCALE_DTYPE = np.dtype([("s", "<f8"), ("at", "<i8"), ("row", "<i4"), ("side", "
 assert TSCALE_DTYPE.itemsize == C.sizeof(PathTscale) == 40
 
 
+# ---- the continuous torque rating: RMS torques, energy, peak power (include/batotp_hip_duty.h) -----------------------------
+DUTY_BLOCK_POINTS = 128             # BATOTP_DUTY_BLOCK_POINTS: points per block of the sum, which is part of the definition
+MAX_LINKS = 8                       # BATOTP_MAX_LINKS
+
+
+class PathDuty(C.Structure):
+    """struct batotp_path_duty"""
+    _fields_ = [("rms", C.c_double * MAX_LINKS), ("util", C.c_double), ("row", C.c_int32), ("n_hold", C.c_int32), ("s", C.c_double),
+                ("s_row", C.c_int32), ("reserved", C.c_int32), ("energy", C.c_double), ("peak_power", C.c_double), ("power_at", C.c_int64),
+                ("n_pts", C.c_int64)]
+
+
+class PathDutySums(C.Structure):
+    """struct batotp_path_duty_sums"""
+    _fields_ = [("S", (C.c_double * 7) * MAX_LINKS), ("W", C.c_double), ("peak_power", C.c_double), ("power_at", C.c_int64), ("n_pts", C.c_int64)]
+
+
+DUTY_DTYPE = np.dtype([("rms", "<f8", (MAX_LINKS,)), ("util", "<f8"), ("row", "<i4"), ("n_hold", "<i4"), ("s", "<f8"), ("s_row", "<i4"),
+                       ("reserved", "<i4"), ("energy", "<f8"), ("peak_power", "<f8"), ("power_at", "<i8"), ("n_pts", "<i8")])
+DUTY_SUMS_DTYPE = np.dtype([("S", "<f8", (MAX_LINKS, 7)), ("W", "<f8"), ("peak_power", "<f8"), ("power_at", "<i8"), ("n_pts", "<i8")])
+assert DUTY_DTYPE.itemsize == C.sizeof(PathDuty) == 128 and DUTY_SUMS_DTYPE.itemsize == C.sizeof(PathDutySums) == 480
+
+
 def _dptr(a: Optional[np.ndarray]):
     if a is None:
         return None
@@ -418,6 +441,26 @@ class Library:
                 fn = getattr(L, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
+
+        # ... and of include/batotp_hip_duty.h (the continuous torque rating), likewise
+        duty_sig = {
+            "batotp_hip_output_duty": [P, C.POINTER(SerialModel), C.c_uint32, D, C.c_double, C.POINTER(P), C.c_void_p, C.c_void_p],
+            "batotp_hip_output_stretch_duty": [P, C.POINTER(Problem), C.POINTER(SerialModel), C.c_uint32, D, C.c_double, I32, C.c_double,
+                                               C.POINTER(P), C.c_void_p, C.c_void_p, C.c_void_p],
+            "batotp_hip_output_duty_ms": [P, C.POINTER(C.c_float)],
+            "batotp_hip_output_duty_ranges": [P, C.POINTER(I32)],
+        }
+        self.duty_symbols = sorted(duty_sig)
+        self.has_duty = all(hasattr(L, name) for name in duty_sig)
+        if self.has_duty:
+            for name, argtypes in duty_sig.items():
+                fn = getattr(L, name)
+                fn.argtypes = argtypes
+                fn.restype = C.c_int
+
+    def need_duty(self):
+        if not self.has_duty:
+            raise BatotpError(f"{self.path} does not export the duty entry points (include/batotp_hip_duty.h)")
 
     def need_tscale(self):
         if not self.has_tscale:
@@ -841,6 +884,58 @@ class Output:
         self.L.need_tscale()
         v = C.c_int32(0)
         self.L.check(self.lib.batotp_hip_output_tscale_ranges(self.handle, C.byref(v)), "output_tscale_ranges")
+        return int(v.value)
+
+    def _rated(self, model: SerialModel, rated) -> np.ndarray:
+        r = np.ascontiguousarray(rated, dtype=np.float64)
+        assert r.shape == (int(model.n_links),), (r.shape, int(model.n_links))
+        return r
+
+    def duty(self, model: SerialModel, rated, target: float = 1.0, host_trig: bool = True, sums: bool = False, flags: Optional[int] = None):
+        """(a NEW Output, records[, sums]): the rows of Output.torques(model) and one DUTY_DTYPE row per path -- the RMS torque of every
+        joint, its utilisation of the continuous torques rated[n_links], the speed factor at which the RMS torque meets target * rated,
+        the mechanical energy and the peak power (batotp_hip_output_duty, include/batotp_hip_duty.h); sums=True: the raw
+        DUTY_SUMS_DTYPE rows the kernels wrote as well"""
+        self.L.need_duty()
+        new = self._like()
+        rec = np.zeros(self.n_paths, dtype=DUTY_DTYPE)
+        raw = np.zeros(self.n_paths, dtype=DUTY_SUMS_DTYPE) if sums else None
+        f = (F_HOST_TRIG if host_trig else 0) if flags is None else int(flags)
+        self.L.check(self.lib.batotp_hip_output_duty(self.handle, C.byref(model), f, _dptr(self._rated(model, rated)), float(target), C.byref(new.handle),
+                                                     rec.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if sums else None),
+                     "batotp_hip_output_duty")
+        new._read_info()
+        return (new, rec, raw) if sums else (new, rec)
+
+    def stretch_duty(self, prob: Problem, model: SerialModel, rated, target: float = 1.0, max_rounds: int = 8, max_factor: float = 16.0,
+                     host_trig: bool = True, flags: Optional[int] = None):
+        """(a NEW Output, report, scale records, duty records): Output.stretch_torques with the RMS family on top -- every path is
+        stretched until its RMS torques are inside target * rated as well (batotp_hip_output_stretch_duty)"""
+        self.L.need_duty()
+        new = self._like()
+        report = np.zeros(self.n_paths, dtype=STRETCH_DTYPE)
+        rec = np.zeros(self.n_paths, dtype=TSCALE_DTYPE)
+        duty = np.zeros(self.n_paths, dtype=DUTY_DTYPE)
+        f = (F_HOST_TRIG if host_trig else 0) if flags is None else int(flags)
+        self.L.check(self.lib.batotp_hip_output_stretch_duty(self.handle, C.byref(prob), C.byref(model), f, _dptr(self._rated(model, rated)), float(target),
+                                                             int(max_rounds), float(max_factor), C.byref(new.handle), report.ctypes.data_as(C.c_void_p),
+                                                             rec.ctypes.data_as(C.c_void_p), duty.ctypes.data_as(C.c_void_p)),
+                     "batotp_hip_output_stretch_duty")
+        new._read_info()
+        return new, report, rec, duty
+
+    def duty_ms(self) -> float:
+        """milliseconds of the duty kernels of the call that made this Output (duty / stretch_duty), all rounds"""
+        self.L.need_duty()
+        v = C.c_float(0)
+        self.L.check(self.lib.batotp_hip_output_duty_ms(self.handle, C.byref(v)), "output_duty_ms")
+        return float(v.value)
+
+    def duty_ranges(self) -> int:
+        """launches of the duty kernel (ranges of paths, over all rounds) of the call that made this Output"""
+        self.L.need_duty()
+        v = C.c_int32(0)
+        self.L.check(self.lib.batotp_hip_output_duty_ranges(self.handle, C.byref(v)), "output_duty_ranges")
         return int(v.value)
 
     def close(self):

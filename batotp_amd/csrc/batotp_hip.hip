@@ -34,7 +34,9 @@
 #include "invdyn.hip.h"
 #include "stretch.hip.h"
 #include "tscale.hip.h"
+#include "duty.hip.h"
 #include "stretch_rounds.h"
+#include "duty_rounds.h"
 
 // Lanes per workgroup of a lane-per-series Thomas solve outside the hot path (resampler, output stage).  Every lane walks its own
 // stream, so a load or store instruction costs its compute unit's address path one cycle per line it touches on top of a fixed ~20
@@ -1931,3 +1933,4 @@ extern "C" int batotp_hip_batch_bytes(batotp_batch *b, int64_t *bytes)
 #include "invdyn_api.inc"
 #include "stretch_api.inc"
 #include "tscale_api.inc"
+#include "duty_api.inc"

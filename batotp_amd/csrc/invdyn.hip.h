@@ -51,10 +51,11 @@ __device__ __forceinline__ void invdyn_stage_model(const batotp_serial_model *__
 }
 
 // Point i < pd.n of a path: copies its joint and Cartesian rows, writes its torque rows (t2 + fv qd) + t4 and leaves the three
-// addends of every joint of the model in t2, fvq and t4.  Every array is indexed by unrolled loops only: they stay in registers.
+// addends of every joint of the model in t2, fvq and t4, and the joint velocities unit * v in q1 (0 beyond n_links; k_duty, duty.hip.h,
+// forms the power from them).  Every array is indexed by unrolled loops only: they stay in registers.
 __device__ __forceinline__ void invdyn_point(const batotp_serial_model &sm, const InvdynPath &pd, int64_t i, const double *__restrict__ src, int nCart,
                                              const double *__restrict__ trig, double *__restrict__ dst, double (&t2)[BATOTP_MAX_LINKS],
-                                             double (&fvq)[BATOTP_MAX_LINKS], double (&t4)[BATOTP_MAX_LINKS])
+                                             double (&fvq)[BATOTP_MAX_LINKS], double (&t4)[BATOTP_MAX_LINKS], double (&q1)[BATOTP_MAX_LINKS])
 {
    const int64_t n = pd.n;
    const int nl = sm.n_links, R = nl + nCart;
@@ -68,7 +69,7 @@ __device__ __forceinline__ void invdyn_point(const batotp_serial_model &sm, cons
    const int64_t ic = i < 1 ? 1 : (i > n - 2 ? n - 2 : i);
    const double c1 = pd.c1, c2 = pd.c2;
 
-   double cq[BATOTP_MAX_LINKS], sq[BATOTP_MAX_LINKS], q1[BATOTP_MAX_LINKS], q2[BATOTP_MAX_LINKS], z[BATOTP_MAX_LINKS];
+   double cq[BATOTP_MAX_LINKS], sq[BATOTP_MAX_LINKS], q2[BATOTP_MAX_LINKS], z[BATOTP_MAX_LINKS];
 #pragma unroll
    for (int j = 0; j < BATOTP_MAX_LINKS; ++j)
    {
@@ -105,6 +106,15 @@ __device__ __forceinline__ void invdyn_point(const batotp_serial_model &sm, cons
          fvq[j] = sm.link[j].fv * q1[j];
          db[(int64_t)(R + j) * n + i] = (t2[j] + fvq[j]) + t4[j];
       }
+}
+
+// the same for a caller that goes on from the three addends alone
+__device__ __forceinline__ void invdyn_point(const batotp_serial_model &sm, const InvdynPath &pd, int64_t i, const double *__restrict__ src, int nCart,
+                                             const double *__restrict__ trig, double *__restrict__ dst, double (&t2)[BATOTP_MAX_LINKS],
+                                             double (&fvq)[BATOTP_MAX_LINKS], double (&t4)[BATOTP_MAX_LINKS])
+{
+   double q1[BATOTP_MAX_LINKS];
+   invdyn_point(sm, pd, i, src, nCart, trig, dst, t2, fvq, t4, q1);
 }
 
 // blocks: points [blk * INVDYN_BP, (blk + 1) * INVDYN_BP) of the path (path: index into the range's descriptors, pathStride bytes each)

@@ -25,6 +25,9 @@ struct batotp_output
    bool fromTscale = false;     // made by batotp_hip_output_torque_scale / _stretch_torques (tscale_api.inc) ...
    float tscaleMs = 0.f;        // ... kernels of tscale.hip.h in that call, all rounds and ranges
    int tscaleRanges = 0;        // ... and how many launches of k_tscale that was
+   bool fromDuty = false;       // made by batotp_hip_output_duty / _stretch_duty (duty_api.inc) ...
+   float dutyMs = 0.f;          // ... kernels of duty.hip.h in that call, all rounds and ranges
+   int dutyRanges = 0;          // ... and how many launches of k_duty that was
 };
 
 extern "C" int batotp_hip_output_destroy(batotp_output *o)

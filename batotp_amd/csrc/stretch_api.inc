@@ -54,6 +54,7 @@ struct StretchRounds
    OutputOwner cur;   // o stretched to n2 (never o itself); nullptr while nothing was stretched
    float ms = 0.f;    // of the stretches
    int launches = 0;
+   const batotp_path_duty *duty = nullptr; // the duty records of the round's K paths, where the RMS family takes part (duty_api.inc)
 
    template <class Evaluate> int run(batotp_output *o, double target, int32_t max_rounds, double max_factor, Evaluate evaluate)
    {
@@ -68,7 +69,8 @@ struct StretchRounds
          if (rc) return rc;
          bool again = false;
          for (int k = 0; k < K; ++k)
-            if (stretchDecide(recs[k], srec ? srec + k : nullptr, target, max_rounds, max_factor, o->n[k], n2[k], state[k])) again = true;
+            if (stretchDecide(recs[k], srec ? srec + k : nullptr, target, max_rounds, max_factor, o->n[k], n2[k], state[k], duty ? duty + k : nullptr))
+               again = true;
          if (!again) return BATOTP_OK;
          batotp_output *next = nullptr;
          if ((rc = stretchRun(o, n2.data(), &next, ms, launches))) return rc;

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "batotp_hip_tscale.h"
+#include "batotp_hip_duty.h"
 
 namespace bk
 {
@@ -22,9 +22,10 @@ struct StretchState
 
 // One path after a round.  a: its audit record; t: its scale record, or nullptr where the torque family takes no part (then the
 // audit's TRQ peak is not read).  A peak of -1 -- not audited, or nothing to evaluate -- passes.  n_in: points of the path before
-// the first round, n2: now.  true: stretch it again, to the new n2.
+// the first round, n2: now.  d: its duty record (include/batotp_hip_duty.h), or nullptr where the RMS family takes no part.
+// true: stretch it again, to the new n2.
 inline bool stretchDecide(const batotp_path_audit &a, const batotp_path_tscale *t, double target, int32_t max_rounds, double max_factor, int64_t n_in,
-                          int64_t &n2, StretchState &s)
+                          int64_t &n2, StretchState &s, const batotp_path_duty *d = nullptr)
 {
    const int velFam[2] = {BATOTP_AUDIT_JNT_VEL, BATOTP_AUDIT_CART_VEL}, accFam[2] = {BATOTP_AUDIT_JNT_ACC, BATOTP_AUDIT_CART_ACC};
    double need = 1.0;
@@ -39,8 +40,14 @@ inline bool stretchDecide(const batotp_path_audit &a, const batotp_path_tscale *
       pass = false;
       if (t->n_static == 0 && t->s < 1.0) need = std::max(need, 1.0 / t->s);
    }
+   const bool rmsPass = !d || d->util <= target || d->util == -1.0;
+   if (!rmsPass)
+   {
+      pass = false;
+      if (d->n_hold == 0 && d->s < 1.0) need = std::max(need, 1.0 / d->s);
+   }
    if (pass) { s.status = BATOTP_STRETCH_PASSES; return false; }
-   if (!trqPass && t->n_static > 0 && kinPass) { s.status = BATOTP_STRETCH_STATIC; return false; }
+   if (kinPass && ((!trqPass && t->n_static > 0) || (!rmsPass && d->n_hold > 0))) { s.status = BATOTP_STRETCH_STATIC; return false; }
    if (s.capped) { s.status = BATOTP_STRETCH_CAPPED; return false; }
    if (s.rounds >= max_rounds) { s.status = BATOTP_STRETCH_ROUNDS; return false; }
    const int64_t m = n2 - 1;

@@ -156,6 +156,22 @@ struct BatchStretch
    bool skipped = false;        // the path carries the output stage's own torque rows and was left as it is
 };
 
+// Extension: the continuous torque rating of one finished trajectory (BA::getLastDuty; the fields of batotp_path_duty,
+// include/batotp_hip_duty.h).
+struct BatchDuty
+{
+   double rms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // RMS torque of every joint
+   double util = -1.;           // largest rms / rated, -1 if none
+   int row = -1;                // its joint
+   int nHold = 0;               // joints whose gravity torque alone reaches target * rated: no stretch helps
+   double s = 0.;               // speed factor at which the RMS torques meet the rating (+Inf: none binds)
+   int sRow = -1;
+   double energy = 0.;          // positive mechanical work over the path
+   double peakPower = 0.;
+   long long powerAt = -1, nPts = 0;
+   bool done = false;           // false: the path failed before the output stage
+};
+
 // defaults of BA::Config (reference ba.h:157-161)
 static const std::vector<double> jntVelLims_init(6, 190);
 static const std::vector<double> jntAccLims_init(6, 500);
@@ -242,7 +258,17 @@ public:
    // switches it off (default: nothing changes).  Defined in ba_tscale.cpp, the only file of the library that refers to the
    // entry points of that header.
    void setStretchToTorqueLimits(double target, int maxRounds = 8, double maxFactor = 16.);
-   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: both stretches off)
+   // Extension: stretch the finished trajectories until their RMS torques are inside the drives' CONTINUOUS torques too
+   // (include/batotp_hip_duty.h): setStretchToTorqueLimits with the RMS family on top.  rated: the continuous torque of every joint
+   // (at least as many as the robot has joints, finite and positive).  When set it takes the place of the torque-stretch step of a
+   // range, under the same preconditions; getLastStretch() reports as it does for that step (status 3 also where gravity alone
+   // reaches a rating) and getLastDuty() holds the RMS torques, utilisation, energy and peak power of the result.  An empty
+   // vector or target <= 0 switches it off (default: nothing changes).  Defined in ba_duty.cpp, the only file of the library
+   // that refers to the entry points of that header.
+   void setStretchToRatedTorques(const std::vector<double> &rated, double target = 1., int maxRounds = 8, double maxFactor = 16.);
+   // one row per path of the last optimizeBatch(), in path order (empty: setStretchToRatedTorques off)
+   const std::vector<BatchDuty> &getLastDuty() const { return _lastDuty; }
+   // one row per path of the last optimizeBatch(), in path order, over all devices and output calls (empty: every stretch off)
    const std::vector<BatchStretch> &getLastStretch() const { return _lastStretch; }
    // Extension: the host half of interpInputData() only (everything before reference
    // ba.cpp:299): leaves the final knot values in traj.theta / traj.cart, the knot spacing in
@@ -435,6 +461,13 @@ private:
    int _tscaleRounds = 8;
    int (*_tscaleFn)(void *output, const void *problem, const void *model, unsigned int flags, double target, int maxRounds, double maxFactor, size_t n,
                     void **out, BatchStretch *report) = nullptr;
+   // batotp_hip_output_stretch_duty behind a pointer; set by setStretchToRatedTorques (ba_duty.cpp)
+   std::vector<double> _dutyRated;
+   double _dutyTarget = 0, _dutyMaxFactor = 16.;
+   int _dutyRounds = 8;
+   int (*_dutyFn)(void *output, const void *problem, const void *model, unsigned int flags, const double *rated, double target, int maxRounds,
+                  double maxFactor, size_t n, void **out, BatchStretch *report, BatchDuty *duty) = nullptr;
+   std::vector<BatchDuty> _lastDuty;
    // batotp_hip_resample_chain / batotp_hip_set_kin_chain behind pointers; set by setToolPoint (ba_kin.cpp)
    int (*_kinResampleFn)(void *ctx, const void *params, const void *chain, int nPaths, const int64_t *nIn, const double *x, const double *sresIn,
                          void **out) = nullptr;

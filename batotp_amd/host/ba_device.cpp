@@ -856,11 +856,18 @@ int BA::optimizeBatch(std::vector<Traj> &trajs)
          for (size_t q = 0; q < worker[d]._lastAudit.size() && lo[d] + q < lo[d + 1]; ++q) _lastAudit[lo[d] + q] = worker[d]._lastAudit[q];
    }
    _lastStretch.clear();
-   if (_stretchFn || _tscaleFn)
+   if (_stretchFn || _tscaleFn || _dutyFn)
    {
       _lastStretch.assign(trajs.size(), BatchStretch());
       for (size_t d = 0; d < nDev; ++d)
          for (size_t q = 0; q < worker[d]._lastStretch.size() && lo[d] + q < lo[d + 1]; ++q) _lastStretch[lo[d] + q] = worker[d]._lastStretch[q];
+   }
+   _lastDuty.clear();
+   if (_dutyFn)
+   {
+      _lastDuty.assign(trajs.size(), BatchDuty());
+      for (size_t d = 0; d < nDev; ++d)
+         for (size_t q = 0; q < worker[d]._lastDuty.size() && lo[d] + q < lo[d + 1]; ++q) _lastDuty[lo[d] + q] = worker[d]._lastDuty[q];
    }
    // what a single-device run leaves in the object (run state a later writeOutputData / interpOutputData reads)
    _isInterpolated = worker[0]._isInterpolated;
@@ -978,7 +985,9 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
    _lastAudit.clear();
    if (_auditFn) _lastAudit.assign(trajs.size(), BatchAudit()); // (setAuditTolerance; a path that fails early keeps audited = false)
    _lastStretch.clear();
-   if (_stretchFn || _tscaleFn) _lastStretch.assign(trajs.size(), BatchStretch()); // (setStretchToLimits, setStretchToTorqueLimits; likewise done = false)
+   if (_stretchFn || _tscaleFn || _dutyFn) _lastStretch.assign(trajs.size(), BatchStretch()); // (setStretchToLimits, setStretchToTorqueLimits, setStretchToRatedTorques; likewise done = false)
+   _lastDuty.clear();
+   if (_dutyFn) _lastDuty.assign(trajs.size(), BatchDuty());
    if (trajs.empty()) return 0;
    if (_isInterpOnly || _sWeights[1] + _sWeights[2] < 1e-8)
    {
@@ -993,7 +1002,9 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
       return -1;
    }
    // stretched until the torque limits pass (setStretchToTorqueLimits): where torque rows would be added, with a model and a range
-   bool stretchTorques = _tscaleFn && !_isTrqConOn && !_isParallelMechOrig && myRobot.serialModel();
+   // (setStretchToRatedTorques: the same step with the RMS family on top, under the same preconditions)
+   const bool withDuty = _dutyFn && _dutyRated.size() >= _nJoints;
+   bool stretchTorques = (_tscaleFn || withDuty) && !_isTrqConOn && !_isParallelMechOrig && myRobot.serialModel();
    for (unsigned int j = 0; stretchTorques && j < _nJoints; ++j)
    {
       const double hi = j < _JntTrqMax.size() ? _JntTrqMax[j] : 0.0, lo = j < _JntTrqMin.size() ? _JntTrqMin[j] : 0.0;
@@ -1309,8 +1320,19 @@ int BA::optimizeBatchOnDevice(std::vector<Traj> &trajs)
          kernelMs += msStage;
          std::vector<BatchStretch> report(cnt);
          void *stretched = nullptr;
-         rc = _tscaleFn(og.o, &prob, myRobot.serialModel(), BATOTP_F_HOST_TRIG, _tscaleTarget, _tscaleRounds, _tscaleMaxFactor, cnt, &stretched, report.data());
-         if (rc) return fail("output_stretch_torques", rc);
+         if (withDuty)
+         {
+            std::vector<BatchDuty> duty(cnt);
+            rc = _dutyFn(og.o, &prob, myRobot.serialModel(), BATOTP_F_HOST_TRIG, _dutyRated.data(), _dutyTarget, _dutyRounds, _dutyMaxFactor, cnt, &stretched,
+                         report.data(), duty.data());
+            if (rc) return fail("output_stretch_duty", rc);
+            for (size_t q = 0; q < cnt; ++q) _lastDuty[live[k0 + q]] = duty[q];
+         }
+         else
+         {
+            rc = _tscaleFn(og.o, &prob, myRobot.serialModel(), BATOTP_F_HOST_TRIG, _tscaleTarget, _tscaleRounds, _tscaleMaxFactor, cnt, &stretched, report.data());
+            if (rc) return fail("output_stretch_torques", rc);
+         }
          batotp_hip_output_destroy(og.o);
          og.o = static_cast<batotp_output *>(stretched);
          for (size_t q = 0; q < cnt; ++q) _lastStretch[live[k0 + q]] = report[q];

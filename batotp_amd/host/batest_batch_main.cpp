@@ -1,7 +1,7 @@
 // batest_batch_main.cpp -- command-line driver of the many-path extension BA::optimizeBatch().
 //
 //   batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]]
-//                [--stretch-torques [target]]
+//                [--stretch-torques [target]] [--stretch-duty R1,R2,... [target]]
 //
 // --audit [tol] (builds with -DBATOTP_HAVE_AUDIT, i.e. the product's): the finished trajectories are audited against the
 // limits on the device (BA::setAuditTolerance, include/batotp_hip_audit.h; tol defaults to 0) and one summary line names
@@ -19,6 +19,10 @@
 // (BA::setStretchToTorqueLimits, include/batotp_hip_tscale.h; target defaults to 1), and carry those torque rows.  One summary
 // line: paths stretched, largest factor, paths not passing, of those the paths no stretch can help; with --audit one more line per
 // path gives the peak utilisation of the torque range.
+// --stretch-duty R1,R2,... [target] (builds with -DBATOTP_HAVE_DUTY, i.e. the product's): as --stretch-torques, and until the RMS
+// torque of every joint is within target of its continuous torque R1, R2, ... too (BA::setStretchToRatedTorques,
+// include/batotp_hip_duty.h; one rating per joint; target defaults to 1).  One summary line, and per path its utilisation of the
+// ratings with the joint, its energy and its peak power.
 // --auto-integ-res leaves BA's class default on (reference ba.h:309; the reference's own driver switches it off,
 // test/main.cpp:53): every path then integrates with the step the rule of ba.cpp:493-556 derives from it.
 // (--host-resample / --host-output are accepted and ignored: since round 4 both stages always run behind the C-ABI.)
@@ -41,7 +45,7 @@ int main(int argc, char *argv[])
 {
    if (argc < 3)
    {
-      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]] [--stretch-torques [target]]\n");
+      fprintf(stderr, "usage: batest_batch config.dat nPaths [--auto-integ-res] [--devices N | --all-devices] [--audit [tol]] [--torques] [--stretch [target]] [--stretch-torques [target]] [--stretch-duty R1,R2,... [target]]\n");
       return 2;
    }
    const int nPaths = atoi(argv[2]);
@@ -60,8 +64,32 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_TSCALE
    double tscaleTarget = 0;
 #endif
+#ifdef BATOTP_HAVE_DUTY
+   double dutyTarget = 0;
+   std::vector<double> dutyRated;
+#endif
    for (int k = 3; k < argc; ++k)
    {
+#ifdef BATOTP_HAVE_DUTY
+      if (std::string(argv[k]) == "--stretch-duty" && k + 1 < argc)
+      {
+         dutyTarget = 1;
+         for (const char *at = argv[++k]; *at;)
+         {
+            char *end = nullptr;
+            dutyRated.push_back(strtod(at, &end));
+            if (end == at) { fprintf(stderr, "--stretch-duty: '%s' is not a list of ratings\n", argv[k]); return 2; }
+            at = *end == ',' ? end + 1 : end;
+         }
+         char *end = nullptr;
+         if (k + 1 < argc)
+         {
+            const double v = strtod(argv[k + 1], &end);
+            if (end != argv[k + 1] && *end == 0 && v > 0 && v <= 1) { dutyTarget = v; ++k; }
+         }
+         continue;
+      }
+#endif
 #ifdef BATOTP_HAVE_TSCALE
       if (std::string(argv[k]) == "--stretch-torques")
       {
@@ -131,6 +159,9 @@ int main(int argc, char *argv[])
 #ifdef BATOTP_HAVE_TSCALE
    planner.setStretchToTorqueLimits(tscaleTarget);
 #endif
+#ifdef BATOTP_HAVE_DUTY
+   planner.setStretchToRatedTorques(dutyRated, dutyTarget);
+#endif
    if (allDevices) nDevices = planner.useAllDevices();
    else if (nDevices > 0)
    {
@@ -189,6 +220,35 @@ int main(int argc, char *argv[])
                 nStretched, (int)st.size(), st[worst].factor, worst, nNotPassing, nStatic);
    }
 #endif
+#ifdef BATOTP_HAVE_DUTY
+   if (dutyTarget > 0)
+   {
+      const std::vector<BatchStretch> &st = planner.getLastStretch();
+      const std::vector<BatchDuty> &du = planner.getLastDuty();
+      int nDone = 0, nStretched = 0, nNotPassing = 0, nStatic = 0, worst = -1;
+      for (size_t p = 0; p < st.size() && p < du.size(); ++p)
+      {
+         if (!st[p].done || !du[p].done) continue;
+         ++nDone;
+         if (st[p].nOut > st[p].nIn) ++nStretched;
+         if (st[p].status != 0) ++nNotPassing;
+         if (st[p].status == 3) ++nStatic;
+         if (worst < 0 || st[p].factor > st[worst].factor) worst = (int)p;
+      }
+      if (nDone == 0)
+         printf("stretch-duty (target %g): not applied (it needs a serial robot planned without torque limits, a chain model, a torque range and a rating per joint)\n",
+                dutyTarget);
+      else
+      {
+         printf("stretch-duty (target %g): %d of %d paths stretched, largest factor %.6f (path %d), %d not passing, %d of them static\n", dutyTarget, nStretched,
+                (int)st.size(), st[worst].factor, worst, nNotPassing, nStatic);
+         for (size_t p = 0; p < du.size(); ++p)
+            if (du[p].done)
+               printf("duty: path %d util %.6g (joint %d) energy %.6f peak_power %.6f (point %lld of %lld)\n", (int)p, du[p].util, du[p].row, du[p].energy,
+                      du[p].peakPower, du[p].powerAt, du[p].nPts);
+      }
+   }
+#endif
 #ifdef BATOTP_HAVE_AUDIT
    if (auditTol >= 0)
    {
@@ -216,6 +276,9 @@ int main(int argc, char *argv[])
       bool trqLines = torques;
 #ifdef BATOTP_HAVE_TSCALE
       trqLines = trqLines || tscaleTarget > 0;
+#endif
+#ifdef BATOTP_HAVE_DUTY
+      trqLines = trqLines || dutyTarget > 0;
 #endif
       if (trqLines)
          for (size_t p = 0; p < audit.size(); ++p)
